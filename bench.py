@@ -9,7 +9,7 @@ by this build's rules core.  Two rates are printed, and the line says which is w
     already in HBM when the timed region starts and the outputs stay in HBM; exactly
     --steps passes are timed (`sustained_evals_per_sec` is the same loop held for >= 5 s; that leg runs
     first, so the --warmup / --steps passes run on a chip already at its steady clocks).
-  * `reference_metric.evals_per_sec` -- the reference's own definition,
+  * `reference_metric.evals_per_sec` (with --full) -- the reference's own definition,
     batchsize.cc:61-79: BatchSize * Repeat / wall over back-to-back computeBlocking calls
     INCLUDING H2D and D2H, held for >= 5 s; `..._distinct_positions` repeats both on B
     distinct positions of random-playout games.
@@ -17,6 +17,12 @@ by this build's rules core.  Two rates are printed, and the line says which is w
 A "step" = one pass of the hot path over one batch: planes -> resnet -> heads.
 One process per GPU; positions shard across ranks with no data-path collective
 (weak scaling); RCCL is used once, to broadcast the weight blob from rank 0.
+
+A plain run sets up, warms up (the sustained leg, then --warmup passes), times --steps passes and prints the
+line; `--dump-outputs DIR` then also writes what the last timed pass computed (policy.npy [B, 2187],
+win_rate.npy [B], draw_rate.npy [B], float32; rank 0's shard) for output-by-output comparison of two builds.
+`--full` adds every other leg: the reference's computeBlocking metric, self-play, other batch sizes, configs
+and precisions, the plane-kernel roofline, clock samples during the sustained leg and the CPU baselines.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (what the driver runs)
@@ -415,6 +421,8 @@ def rehearse_cpu(args, rank, world):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, pol, win, drw)
         print(json.dumps({
             "metric": f"NN evals/sec at batch={B}", "value": B * args.steps * world / dt, "unit": "evals/s",
             "n_gpus": world, "ranks_seen": ranks_seen, "steps": args.steps, "warmup": args.warmup,
@@ -424,6 +432,13 @@ def rehearse_cpu(args, rank, world):
                                    f"infer::Random stand-in executor on the host, {world} rank(s) over gloo",
                        "batch_per_gpu": B, "weights_broadcast_bytes": blob_bytes}}))
     return 0
+
+
+def dump_outputs(directory, policy, win, draw):
+    """--dump-outputs: the arrays a caller of the timed path receives, as DIR/<name>.npy (float32)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in (("policy", policy), ("win_rate", win), ("draw_rate", draw)):
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def sample_clock(gpu, out, stop, period=1.0):
@@ -483,10 +498,19 @@ def main():
                     help="no rocm-smi child processes during the sustained leg (under rocprofv3 the box refuses a "
                          "profiled process's children that exec another program)")
     ap.add_argument("--no-host-path", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline line: the reference's computeBlocking metric, self-play, "
+                         "other batch sizes / configs / precisions, the plane-kernel roofline, rocm-smi clock samples "
+                         "during the sustained leg, CPU baselines (the --no-* / --selfplay-* options shape them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the outputs of the last one as DIR/policy.npy, win_rate.npy, "
+                         "draw_rate.npy (float32; rank 0's shard)")
     ap.add_argument("--executor", default="hip", choices=["hip", "random"],
                     help="hip: the MI355X evaluator (the benchmark).  random: CPU rehearsal of the multi-rank path -- "
                          "gloo backend, the reference's EXECUTOR=random stand-in as the executor, no GPU touched")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- ranks.  The driver starts N ranks with torch.distributed.run; started WITHOUT a launcher and with
     # --gpus N > 1 this process becomes the launcher (the reference multiplies executors from one command,
@@ -585,7 +609,7 @@ def main():
         clock_samples, clock_stop = [], threading.Event()
         sampler = None
         profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
-        if rank == 0 and not args.no_clock_sample and not profiled:
+        if rank == 0 and args.full and not args.no_clock_sample and not profiled:
             # the chip runs this kernel power-limited: the clock it HOLDS under the load is sampled live
             sampler = threading.Thread(target=sample_clock, args=(local_rank, clock_samples, clock_stop), daemon=True)
             sampler.start()
@@ -621,11 +645,13 @@ def main():
     if distributed:
         dt = nsg.dist.max_over_ranks(dt, device="cuda")
     ev.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *ev.download_outputs(B))
 
     # ---- metric #2: self-play games/sec (each rank drives its own GPU; games shard
     # embarrassingly, no collective on the data path)
     sp = None
-    if args.selfplay_seconds > 0 and os.path.exists(SELFPLAY_BIN):
+    if args.full and args.selfplay_seconds > 0 and os.path.exists(SELFPLAY_BIN):
         import tempfile
         fd, wpath = tempfile.mkstemp(prefix=f"nsg_bench_weights_r{rank}_", suffix=".nsgw")
         with os.fdopen(fd, "wb") as f:  # every rank writes its own copy of the broadcast bytes
@@ -691,7 +717,8 @@ def main():
     # computeBlocking incl. H2D / D2H on the initial position replicated B times; whole job = sum over ranks
     ref = None
     hostev = None
-    if not args.no_host_path:
+    host_path = args.full and not args.no_host_path
+    if host_path:
         hostev = nsg.Evaluator(local_rank, B, 86, precision=args.precision)
         hostev.load_memory(blob)
         pol = np.empty((B, 2187), np.float32)
@@ -739,7 +766,7 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": DTYPE_NAME[args.precision], "data": "synthetic",
             "value_is": "device-resident rate (bitboards in HBM, outputs left in HBM); the reference's own "
-                        "PCIe-inclusive definition is reference_metric.evals_per_sec; the timed steps follow the "
+                        "PCIe-inclusive definition is reference_metric.evals_per_sec (--full); the timed steps follow the "
                         "sustained leg, i.e. run at the chip's steady clocks",
             "config": {"workload": f"batch={B} x {blocks}-block x {channels}-channel policy/value/draw "
                                    f"resnet, 86 feature planes, device-resident bitboards -> planes -> "
@@ -843,11 +870,11 @@ def main():
             rev.upload_features(bb)
             out["roofline_extract"] = extract_roofline(nsg, rev, bb, B, args.precision)
             rev.close()
-        if not args.no_host_path and world == 1:
+        if host_path and world == 1:
             out["other_precisions_evals_per_sec"] = {
                 p: quick_rate(nsg, local_rank, blob, bb, B, p) for p in ("fp32", "f16x3", "f16m8", "f16m6", "fp16", "bf16")
                 if p != args.precision}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # N = 1 only (the measurement contract): at N > 1 the other ranks would spin in a collective on the host
             # cores this leg measures
             out["cpu_baseline"] = cpu_baseline(nsg)

@@ -6,10 +6,10 @@ TAG=$1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/final_$TAG
 mkdir -p $OUT
-python3 bench.py > $OUT/bench_default_f16m8.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default_f16m8.json 2> $OUT/bench_default.err
 echo "bench default done"
-python3 bench.py --precision f16x3 --selfplay-seconds 0 --no-cpu-baseline > $OUT/bench_f16x3.json 2>> $OUT/bench_default.err
-python3 bench.py --precision fp32 --selfplay-seconds 0 --no-cpu-baseline > $OUT/bench_fp32.json 2>> $OUT/bench_default.err
+python3 bench.py --full --precision f16x3 --selfplay-seconds 0 --no-cpu-baseline > $OUT/bench_f16x3.json 2>> $OUT/bench_default.err
+python3 bench.py --full --precision fp32 --selfplay-seconds 0 --no-cpu-baseline > $OUT/bench_fp32.json 2>> $OUT/bench_default.err
 for prec in f16m8 f16x3 fp32; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$prec -- python3 bench.py --precision $prec --selfplay-seconds 0 --no-cpu-baseline --no-host-path --steps 6 --warmup 2 > $OUT/kt_$prec.log 2>&1
   cp $(find $OUT/kt_$prec -name "*kernel_stats.csv" | head -1) $OUT/${prec}_b512_20x256_kernel_stats.csv
