@@ -284,6 +284,12 @@ int nsg_get_team_stats(nsg_evaluator* ev, int* enabled, int* members_last, uint6
  * *coop_enabled: 1 in use, 0 off (not applicable, switched off, or after a fallback), -1 another process holds the
  * device's token. */
 int nsg_get_last_launch_kind(nsg_evaluator* ev, int* kind, int* coop_enabled);
+/* What nsg_get_last_launch_kind and nsg_get_last_plan leave apart about the most recent forward pass:
+ * *whole_trunk: 1 when every 3x3 layer ran as ONE persistent launch whose workgroups own whole boards (reported as
+ * kind 0 above), else 0; *parts: the number of parts when the batch ran as a full part plus remainder parts with
+ * their own plans (nsg_get_last_plan's chains counts those and half-batch chains alike), 0 when it did not.
+ * Both 0 before the first pass. */
+int nsg_get_last_launch_form(nsg_evaluator* ev, int* whole_trunk, int* parts);
 
 /* Launch plan of the most recent forward pass (tests and tuning): boards per
  * workgroup, 16-channel fragments per wave, waves per workgroup, and the number

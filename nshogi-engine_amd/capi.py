@@ -105,6 +105,7 @@ def load_library():
     lib.nsg_get_last_plan.argtypes = [vp, ip, ip, ip, ip]
     lib.nsg_get_team_stats.argtypes = [vp, ip, ip, ctypes.POINTER(ctypes.c_uint64)]
     lib.nsg_get_last_launch_kind.argtypes = [vp, ip, ip]
+    lib.nsg_get_last_launch_form.argtypes = [vp, ip, ip]
     lib.nsg_get_last_trunk_precision.argtypes = [vp, ip]
     lib.nsg_get_last_split.argtypes = [vp, ip, ip]
     lib.nsg_get_last_slab_split.argtypes = [vp, ip]
@@ -324,6 +325,13 @@ class Evaluator:
         k, c = ctypes.c_int(), ctypes.c_int()
         _check(self._lib.nsg_get_last_launch_kind(self._h, ctypes.byref(k), ctypes.byref(c)))
         return {0: "per_layer", 1: "team", 2: "coop"}.get(k.value, k.value), c.value
+
+    def last_launch_form(self):
+        """nsg_get_last_launch_form: {"whole_trunk": 1 / 0 (every 3x3 layer in one launch without hand-off),
+        "parts": parts of a two-part batch (0: the batch was not split into parts)}."""
+        wt, parts = ctypes.c_int(), ctypes.c_int()
+        _check(self._lib.nsg_get_last_launch_form(self._h, ctypes.byref(wt), ctypes.byref(parts)))
+        return {"whole_trunk": wt.value, "parts": parts.value}
 
     def last_plan(self):
         """Launch plan of the most recent forward pass (nsg_get_last_plan)."""

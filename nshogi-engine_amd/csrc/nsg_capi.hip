@@ -344,6 +344,8 @@ struct nsg_evaluator {
     int coopEnabled = 1;
     int coopForced = 0;         // NSG_COOP_TRUNK=1: wherever a plan allows it; unset: where it measured faster (enqueueForward)
     int lastPersistent = 0;     // what the most recent forward ran: 0 per-layer / persistent-without-hand-off, 1 team trunk, 2 cooperative trunk
+    int lastWholeTrunk = 0;     // the most recent forward ran every 3x3 layer as ONE launch without hand-off (launchTrunk)
+    int lastParts = 0;          // ... as a two-part batch of this many parts (0: not split into parts)
     int coopFaultXccLaunches = 0; // NSG_COOP_FAULT_XCC_LAUNCHES (test hook), see enqueueCoop
     int teamFaultLaunches = 0;  // NSG_TEAM_FAULT_LAUNCHES (test hook): this many team launches are made ONE WORKGROUP SHORT,
                                 // so that the team waits in vain, gives up and the recovery path runs
@@ -837,6 +839,8 @@ int enqueueForward(nsg_evaluator* ev, size_t n) {
     // has a team launch in flight on this device.
     ev->teamLast = false;
     ev->lastPersistent = 0;
+    ev->lastWholeTrunk = 0;
+    ev->lastParts = 0;
     // (a give-up word still raised here belongs to a forward nobody waited for: its batch is gone, the team path is not
     // taken again)
     if (ev->teamStatusHost && *ev->teamStatusHost != 0) {
@@ -961,6 +965,7 @@ int enqueueForward(nsg_evaluator* ev, size_t n) {
     if (nParts > 0) {
         ev->lastPlan = parts[0].plan;
         ev->lastChains = nParts;
+        ev->lastParts = nParts;
         NSG_HIP(hipEventRecord(ev->forkEvent, s));
         if (prof) NSG_HIP(hipEventRecord(e[1], s));
         for (int c = 0; c < nParts; ++c) {
@@ -978,6 +983,7 @@ int enqueueForward(nsg_evaluator* ev, size_t n) {
     if (chains == 1 && trunkKernel) {
         // one persistent launch for all 2N+1 3x3 layers (measured slower; NSG_TRUNK_KERNEL=1)
         const int prec = ev->prec;
+        ev->lastWholeTrunk = 1;
         NSG_HIP(nsg::launchExtractBitsAct(ev->planes.p, (const uint64_t*)ev->input.p, B, ev->numChannels,
                                           ev->cpad, prec, s));
         if (prof) NSG_HIP(hipEventRecord(e[1], s));
@@ -1842,6 +1848,13 @@ int nsg_get_last_launch_kind(nsg_evaluator* ev, int* kind, int* coop_enabled) {
     if (!ev) return fail(NSG_E_INVALID, "null evaluator");
     if (kind) *kind = ev->lastPersistent;
     if (coop_enabled) *coop_enabled = ev->coopEnabled ? 1 : (ev->teamLockedOut ? -1 : 0);
+    return NSG_OK;
+}
+
+int nsg_get_last_launch_form(nsg_evaluator* ev, int* whole_trunk, int* parts) {
+    if (!ev) return fail(NSG_E_INVALID, "null evaluator");
+    if (whole_trunk) *whole_trunk = ev->lastWholeTrunk;
+    if (parts) *parts = ev->lastParts;
     return NSG_OK;
 }
 
