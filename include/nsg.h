@@ -96,13 +96,21 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  * ONNX model file the engine passes (trt.cc:121-131, default
  * ./res/model.onnx, src/context.h:93) or an NSGW v1 weight file (DESIGN.md
  * "Weight file"); the two are told apart by their first bytes.  An ONNX model
- * must be of the topology family this library runs (csrc/onnx_reader.h) and
- * obey the reference's tensor contract (input "input", outputs "policy",
- * "value", "draw", trt.cc:144-150,193-227); anything else fails with
- * NSG_E_FORMAT and a message naming the node (the reference's parser failure,
- * trt.cc:127-131).  BN is folded and the weights are re-laid into MFMA
- * fragment order on upload.  The policy width is checked against
- * NSG_MOVE_INDEX_MAX as trt.cc:193-210 does. */
+ * must obey the reference's tensor contract (input "input" [N,C,9,9] with C =
+ * num_channels, outputs "policy" with NSG_MOVE_INDEX_MAX values per position,
+ * "value", "draw", trt.cc:144-150,193-227).  It loads on one of two paths:
+ *  - the specialised path, when it is of the topology family this library's
+ *    tuned kernels run (csrc/onnx_reader.h) and that loader accepts it (trunk
+ *    and value-hidden widths multiples of 64).  It runs at the evaluator's
+ *    precision (nsg_set_precision);
+ *  - otherwise the general graph path, when the model
+ *    is built only from its closed op set.  A general graph always runs in
+ *    exact fp32, whatever nsg_set_precision asked for.
+ * When both refuse, the load fails with NSG_E_FORMAT and a message giving both
+ * reasons, the general path's naming the node (the reference's parser
+ * failure, trt.cc:127-131).  nsg_set_graph_mode(ev, 1) sends every ONNX model
+ * to the general path.  An NSGW blob always loads on the specialised path.
+ * BN is folded and the weights are re-laid for the kernels on upload. */
 int nsg_load(nsg_evaluator* ev, const char* path);
 /* The ONNX -> NSGW v1 conversion nsg_load applies, on host memory and with no
  * device: writes *nsgw_size and, if dst != NULL, the blob (capacity bytes
@@ -312,6 +320,34 @@ int nsg_get_last_slab_split(nsg_evaluator* ev, int* slab_split);
  * the first pass).  An F16M8 evaluator runs small batches for which it has no F16M8 tile plan
  * (channel counts other than 256) as F16X3. */
 int nsg_get_last_trunk_precision(nsg_evaluator* ev, int* precision);
+
+/* ---- the general graph path ---- */
+#define NSG_GRAPH_AUTO 0    /* ONNX: the specialised path when it accepts the model, else the general path */
+#define NSG_GRAPH_FORCE 1   /* ONNX: the general path even for family models (cross-checks, benchmarks) */
+#define NSG_PATH_SPECIALISED 0
+#define NSG_PATH_GRAPH 1
+/* Chooses how the next nsg_load* treats an ONNX model (NSG_GRAPH_*).  Must be
+ * called before nsg_load*.  NSGW blobs are not affected. */
+int nsg_set_graph_mode(nsg_evaluator* ev, int mode);
+typedef struct nsg_graph_info {
+    int path;            /* NSG_PATH_SPECIALISED or NSG_PATH_GRAPH */
+    int precision;       /* arithmetic of the network: a general graph is always NSG_PRECISION_FP32 */
+    int nodes;           /* nodes of the ONNX graph */
+    int launches;        /* general path: kernel launches per forward (plane expansion and output scatter
+                            included); specialised path: 0 */
+    int conv_launches;   /* general path: convolution and dense-layer launches per forward; specialised: 0 */
+    int reserved;
+    uint64_t param_count;      /* float constants of the model */
+    double flops_per_position; /* general path: every conv and dense layer; specialised: as nsg_info's */
+    uint64_t activation_bytes_per_position; /* general path: device activation buffers per board; specialised: 0 */
+    uint64_t activation_bytes; /* ... allocated for BatchSizeMax (0 from nsg_inspect_onnx) */
+} nsg_graph_info;
+/* What the loaded network runs on.  NSG_E_NOT_LOADED before a load. */
+int nsg_get_graph_info(nsg_evaluator* ev, nsg_graph_info* info);
+/* The load decision and the general path's planning, on the host with no
+ * device: fills *info for the path nsg_load would take with `num_channels`
+ * input planes, or fails with NSG_E_FORMAT and nsg_load's message. */
+int nsg_inspect_onnx(const void* onnx, size_t size, int num_channels, nsg_graph_info* info);
 
 /* CPU stand-in executors of the reference (src/infer/zero.cc, nothing.cc,
  * random.cc): product code, selectable like EXECUTOR=zero|nothing|random

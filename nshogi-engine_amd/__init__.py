@@ -16,6 +16,7 @@ from .capi import (  # noqa: F401
     CpuExecutor,
     extract_bits,
     convert_onnx,
+    inspect_onnx,
     load_library,
     library_path,
     PRECISION_FP32,
@@ -29,7 +30,7 @@ from .capi import (  # noqa: F401
 from . import weights, synth, dist, onnx_io, teacher, positions  # noqa: F401
 
 __all__ = [
-    "NsgError", "Evaluator", "CpuExecutor", "extract_bits", "convert_onnx", "load_library",
+    "NsgError", "Evaluator", "CpuExecutor", "extract_bits", "convert_onnx", "inspect_onnx", "load_library",
     "library_path", "weights", "synth", "dist", "onnx_io", "teacher", "positions", "PRECISION_FP32", "PRECISION_FP16",
     "PRECISION_BF16", "PRECISION_F16X3", "PRECISION_F16M8", "MOVE_INDEX_MAX", "NUM_SQUARES",
 ]

@@ -58,6 +58,25 @@ class _Info(ctypes.Structure):
     ]
 
 
+class _GraphInfo(ctypes.Structure):
+    _fields_ = [
+        ("path", ctypes.c_int), ("precision", ctypes.c_int), ("nodes", ctypes.c_int),
+        ("launches", ctypes.c_int), ("conv_launches", ctypes.c_int), ("reserved", ctypes.c_int),
+        ("param_count", ctypes.c_uint64), ("flops_per_position", ctypes.c_double),
+        ("activation_bytes_per_position", ctypes.c_uint64), ("activation_bytes", ctypes.c_uint64),
+    ]
+
+
+_PATH_NAMES = {0: "specialised", 1: "graph"}
+
+
+def _graph_info_dict(s):
+    d = {k: getattr(s, k) for k, _ in _GraphInfo._fields_ if k != "reserved"}
+    d["path"] = _PATH_NAMES.get(s.path, s.path)
+    d["precision"] = {v: k for k, v in _PREC_NAMES.items() if k not in ("f32", "f16")}.get(s.precision, s.precision)
+    return d
+
+
 def load_library():
     """Loads csrc/libnsg.so.  Fails loudly: there is no Python/CPU fallback."""
     global _lib
@@ -111,6 +130,9 @@ def load_library():
     lib.nsg_get_last_slab_split.argtypes = [vp, ip]
     lib.nsg_compute_gather_blocking.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp]
     lib.nsg_compute_gather_nonblocking.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp]
+    lib.nsg_set_graph_mode.argtypes = [vp, i]
+    lib.nsg_get_graph_info.argtypes = [vp, ctypes.POINTER(_GraphInfo)]
+    lib.nsg_inspect_onnx.argtypes = [vp, sz, i, ctypes.POINTER(_GraphInfo)]
     lib.nsg_cpu_executor_create.argtypes = [i, ctypes.c_uint64, ctypes.POINTER(vp)]
     lib.nsg_cpu_executor_destroy.argtypes = [vp]
     lib.nsg_cpu_executor_compute.argtypes = [vp, vp, sz, vp, vp, vp]
@@ -181,6 +203,19 @@ class Evaluator:
     def load_shared(self, src):
         """nsg_load_shared: adopt the network another evaluator has loaded (no file re-read)."""
         _check(self._lib.nsg_load_shared(self._h, src._h))
+
+    def set_graph_mode(self, mode):
+        """nsg_set_graph_mode (before load): 0 / "auto" -- ONNX models the specialised path accepts load there, the
+        rest on the general graph path; 1 / "force" -- every ONNX model on the general graph path."""
+        m = {"auto": 0, "force": 1}.get(mode, mode)
+        _check(self._lib.nsg_set_graph_mode(self._h, int(m)))
+
+    def graph_info(self):
+        """nsg_get_graph_info: the path the loaded network runs on ("specialised" | "graph"), its arithmetic, ONNX
+        nodes, launches and conv launches per forward, parameters, FLOPs per position, activation bytes."""
+        s = _GraphInfo()
+        _check(self._lib.nsg_get_graph_info(self._h, ctypes.byref(s)))
+        return _graph_info_dict(s)
 
     def _outputs(self, n, policy, win, draw):
         if policy is None:
@@ -394,6 +429,16 @@ def convert_onnx(data):
     out = np.empty(need.value, dtype=np.uint8)
     _check(lib.nsg_convert_onnx(_ptr(buf), buf.size, _ptr(out), out.size, ctypes.byref(need)))
     return out.tobytes()
+
+
+def inspect_onnx(data, num_channels=86):
+    """nsg_inspect_onnx: would this ONNX model load, and how (graph_info's dict), on the host with no device.
+    Raises NsgError (NSG_E_FORMAT) with nsg_load's message otherwise."""
+    lib = load_library()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    s = _GraphInfo()
+    _check(lib.nsg_inspect_onnx(_ptr(buf) if buf.size else None, buf.size, int(num_channels), ctypes.byref(s)))
+    return _graph_info_dict(s)
 
 
 def extract_bits(dst_ptr, src_ptr, batch_size, num_channels, channels_first=True, stream=0):

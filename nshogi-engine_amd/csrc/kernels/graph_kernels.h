@@ -1,0 +1,74 @@
+// graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_ops.hip).
+//
+// Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
+// innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
+#ifndef NSG_GRAPH_KERNELS_H
+#define NSG_GRAPH_KERNELS_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../onnx_graph.h"
+
+namespace nsg {
+namespace graph {
+
+struct DevView {
+    const float* p = nullptr;
+    int stride = 0, offset = 0, C = 0;
+};
+
+// Implicit-GEMM convolution on the f32 MFMA (v_mfma_f32_16x16x4_f32): M = groups x 81 rows, N = output channels,
+// K = taps x cinPad.  taps 9: a 3x3 conv of `groups` boards; taps 1: a 1x1 conv, or a dense layer when the rows are
+// boards (then `groups` = ceil(boards / 81) and `rows` masks the last group).  w: packed [coutTiles][cinPad/16][taps]
+// [16][64]; bias [coutTiles * 64].  y = act(acc + bias[c] (+ res)), written for rows < `rows`, channels < out stride.
+hipError_t launchGraphConv(const float* in, int inStride, const float* w, const float* bias, DevView res,
+                           float* out, int outStride, int cout, int cinPad, int coutTiles, int taps, int groups,
+                           long rows, int act, hipStream_t stream);
+
+// Fused elementwise chain (the program of onnx_graph.h's EltInstr / EltSrc) over `rows` rows.
+struct EltArgs {
+    const float* src[kMaxEltSrcs];
+    int stride[kMaxEltSrcs];
+    int offset[kMaxEltSrcs];
+    int mode[kMaxEltSrcs];
+    float scalar[kMaxEltSrcs];
+    uint32_t code[kMaxEltCode]; // op | dst << 8 | a << 16 | b << 24
+    int ncode;
+    int outReg;
+    float* out;
+    int outStride;
+    int C;
+    long rows;
+};
+hipError_t launchGraphElt(const EltArgs& a, hipStream_t stream);
+
+// Mean over the 81 squares: [B*81][in] -> [B][outStride]
+hipError_t launchGraphMean(DevView in, float* out, int outStride, int boards, hipStream_t stream);
+
+// Channel concat (also a plain copy of one view): up to kMaxCopySegs views placed at channel dstOff[i]
+struct ConcatArgs {
+    const float* src[kMaxCopySegs];
+    int stride[kMaxCopySegs];
+    int offset[kMaxCopySegs];
+    int count[kMaxCopySegs];
+    int dstOff[kMaxCopySegs];
+    int nseg;
+    float* out;
+    int outStride;
+    long rows;
+};
+hipError_t launchGraphConcat(const ConcatArgs& a, hipStream_t stream);
+
+// [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)
+hipError_t launchGraphFlatten(DevView in, float* out, int outStride, int boards, hipStream_t stream);
+
+// The evaluator's outputs: policy [B][2187] (from a spatial view read as c * 81 + square, or a flat view), value and
+// draw [B] (flat views of one channel)
+hipError_t launchGraphOutputs(DevView policy, bool policySpatial, DevView value, DevView draw, float* dstPolicy,
+                              float* dstValue, float* dstDraw, int boards, hipStream_t stream);
+
+} // namespace graph
+} // namespace nsg
+
+#endif

@@ -9,6 +9,8 @@
 #include "../../include/nsg.h"
 #include "kernels/kernels.h"
 #include "onnx_reader.h"
+#include "onnx_graph.h"
+#include "kernels/graph_kernels.h"
 
 #include <hip/hip_runtime.h>
 
@@ -38,7 +40,7 @@ namespace {
 thread_local std::string gLastError;
 
 int fail(int code, const char* fmt, ...) {
-    char buf[512];
+    char buf[2048];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
@@ -162,6 +164,21 @@ struct NetWeights {
     }
 };
 
+// The general graph path: the immutable plan and its constants uploaded to one device.
+// Evaluators of that device share it (nsg_load_shared); activation buffers are each evaluator's own.
+struct GraphWeights {
+    int gpu = 0;
+    std::shared_ptr<const nsg::graph::GraphPlan> plan;
+    DevBuf w;
+    ~GraphWeights() {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+        (void)hipSetDevice(gpu);
+        w.release();
+        if (cur >= 0) (void)hipSetDevice(cur);
+    }
+};
+
 // Parsed view of an NSGW v1 blob (DESIGN.md "Weight file").
 struct NetView {
     int cin, F, blocks, pc, vc, vh;
@@ -213,6 +230,20 @@ int parseBlob(const void* blob, size_t size, NetView* nv) {
     nv->fc1B = f; f += VH;
     nv->fc2W = f; f += 2 * VH;
     nv->fc2B = f; f += 2;
+    return NSG_OK;
+}
+
+// What the specialised loader refuses in a parsed blob (NSG_E_FORMAT): an ONNX model it refuses goes to the general
+// graph path instead.
+int checkSpecialised(const NetView& nv, int numChannels) {
+    if (nv.cin != numChannels)
+        return fail(NSG_E_FORMAT, "weight file expects %d input planes, evaluator has %d", nv.cin, numChannels);
+    // trt.cc:193-210: the policy output must have ml::MoveIndexMax elements
+    if (nv.pc * NSG_NUM_SQUARES != NSG_MOVE_INDEX_MAX)
+        return fail(NSG_E_FORMAT, "Unexpected PolicySize: %d (expected: %d).",
+                    nv.pc * NSG_NUM_SQUARES, NSG_MOVE_INDEX_MAX);
+    if (nv.F % 64 != 0) return fail(NSG_E_FORMAT, "trunk width %d is not a multiple of 64", nv.F);
+    if (nv.vh % 64 != 0) return fail(NSG_E_FORMAT, "value hidden width %d is not a multiple of 64", nv.vh);
     return NSG_OK;
 }
 
@@ -302,6 +333,12 @@ struct nsg_evaluator {
     DevBuf scratch;       // debug read-back
 
     std::shared_ptr<NetWeights> W; // shared by the evaluators of one device (nsg_load_shared)
+    // general graph path: set instead of W when the loaded network runs on it
+    std::shared_ptr<GraphWeights> G;
+    DevBuf gPlanes;               // [batchMax * 81][planeStride] f32 input planes
+    std::vector<DevBuf> gAct;     // the plan's activation buffers, sized for batchMax
+    int graphMode = 0;            // nsg_set_graph_mode
+    int loadedNodes = 0;          // ONNX nodes of a family model on the specialised path (0: an NSGW blob)
     int lastTrunkPrec = -1; // precision the most recent forward ran its trunk in
     // host statistics (mcts::Statistics evaluationCount / batchSizeAccumulated, statistics.h:74-98)
     uint64_t statBatches = 0, statPositions = 0;
@@ -818,10 +855,107 @@ nsg::ConvPlan planForBatch(nsg_evaluator* ev, int B) {
     return plan;
 }
 
+// A forward pass of the general graph path: the plane expansion, the plan's launches in order, the output scatter.
+// Always exact fp32; profiling brackets the span from the first to the last conv / dense launch as "trunk".
+int enqueueGraph(nsg_evaluator* ev, int B) {
+    namespace gr = nsg::graph;
+    hipStream_t s = ev->stream;
+    const gr::GraphPlan& P = *ev->G->plan;
+    const float* wts = (const float*)ev->G->w.p;
+    auto ptr = [&](const gr::View& v) -> float* { return v.buf < 0 ? (float*)ev->gPlanes.p : (float*)ev->gAct[(size_t)v.buf].p; };
+    auto dv = [&](const gr::View& v) {
+        gr::DevView d;
+        d.p = ptr(v); d.stride = v.stride; d.offset = v.offset; d.C = v.C;
+        return d;
+    };
+    auto rowsOf = [&](const gr::View& v) -> long { return v.spatial ? (long)B * 81 : (long)B; };
+    const bool prof = ev->profile;
+    if (prof && ev->evUsed + 4 > (int)ev->ev.size()) {
+        int rc = drainProfile(ev);
+        if (rc) return rc;
+    }
+    hipEvent_t* e = prof ? &ev->ev[ev->evUsed] : nullptr;
+    if (prof) NSG_HIP(hipEventRecord(e[0], s));
+    ev->teamLast = false;
+    ev->lastPersistent = 0;
+    ev->lastWholeTrunk = 0;
+    ev->lastParts = 0;
+    ev->lastPlan = nsg::ConvPlan{0, 0, 0};
+    ev->lastChains = 0;
+    ev->lastTrunkPrec = nsg::kFp32;
+    ev->trunkOut = nullptr;
+    NSG_HIP(nsg::launchExtractBitsAct(ev->gPlanes.p, (const uint64_t*)ev->input.p, B, ev->numChannels, P.planeStride,
+                                      nsg::kFp32, s));
+    if (prof && P.convLaunches == 0) { NSG_HIP(hipEventRecord(e[1], s)); NSG_HIP(hipEventRecord(e[2], s)); }
+    int convs = 0;
+    for (const gr::Launch& L : P.launches) {
+        switch (L.kind) {
+        case gr::kLaunchConv: {
+            if (prof && convs == 0) NSG_HIP(hipEventRecord(e[1], s));
+            gr::DevView res;
+            if (L.res.buf != -2) res = dv(L.res);
+            const int groups = L.dense ? (B + 80) / 81 : B;
+            NSG_HIP(gr::launchGraphConv(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out), L.out.stride,
+                                        L.out.C, L.cinPad, L.coutTiles, L.taps, groups, rowsOf(L.out), L.act, s));
+            if (prof && ++convs == P.convLaunches) NSG_HIP(hipEventRecord(e[2], s));
+            break;
+        }
+        case gr::kLaunchElt: {
+            gr::EltArgs a{};
+            for (size_t i = 0; i < L.srcs.size(); ++i) {
+                const gr::EltSrc& S = L.srcs[i];
+                a.mode[i] = S.mode;
+                a.scalar[i] = S.scalar;
+                if (S.mode == gr::kSrcChannel) a.src[i] = wts + S.constOff;
+                else if (S.mode != gr::kSrcScalar) { a.src[i] = ptr(S.v); a.stride[i] = S.v.stride; a.offset[i] = S.v.offset; }
+            }
+            for (size_t i = 0; i < L.code.size(); ++i)
+                a.code[i] = (uint32_t)L.code[i].op | (uint32_t)L.code[i].dst << 8 | (uint32_t)L.code[i].a << 16 | (uint32_t)L.code[i].b << 24;
+            a.ncode = (int)L.code.size();
+            a.outReg = L.eltOut;
+            a.out = ptr(L.out);
+            a.outStride = L.out.stride;
+            a.C = L.out.C;
+            a.rows = rowsOf(L.out);
+            NSG_HIP(gr::launchGraphElt(a, s));
+            break;
+        }
+        case gr::kLaunchMean:
+            NSG_HIP(gr::launchGraphMean(dv(L.in), ptr(L.out), L.out.stride, B, s));
+            break;
+        case gr::kLaunchConcat: {
+            gr::ConcatArgs a{};
+            for (size_t i = 0; i < L.segs.size(); ++i) {
+                a.src[i] = ptr(L.segs[i].v); a.stride[i] = L.segs[i].v.stride; a.offset[i] = L.segs[i].v.offset;
+                a.count[i] = L.segs[i].v.C; a.dstOff[i] = L.segs[i].dstOff;
+            }
+            a.nseg = (int)L.segs.size();
+            a.out = ptr(L.out);
+            a.outStride = L.out.stride;
+            a.rows = rowsOf(L.out);
+            NSG_HIP(gr::launchGraphConcat(a, s));
+            break;
+        }
+        default: // kLaunchFlatten
+            NSG_HIP(gr::launchGraphFlatten(dv(L.in), ptr(L.out), L.out.stride, B, s));
+            break;
+        }
+    }
+    NSG_HIP(gr::launchGraphOutputs(dv(P.policy), P.policy.spatial, dv(P.value), dv(P.draw), (float*)ev->policy.p,
+                                   (float*)ev->value.p, (float*)ev->draw.p, B, s));
+    if (prof) {
+        NSG_HIP(hipEventRecord(e[3], s));
+        ev->evUsed += 4;
+        ev->pendingTrunkLaunchesPerFwd = P.convLaunches;
+    }
+    return NSG_OK;
+}
+
 int enqueueForward(nsg_evaluator* ev, size_t n) {
     const int B = (int)n;
     ++ev->statBatches;
     ev->statPositions += n;
+    if (ev->G) return enqueueGraph(ev, B); // the general graph path: none of the plan / team / chain logic below
     hipStream_t s = ev->stream;
     // the tile plan is chosen for the whole batch: all chains run concurrently
     nsg::ConvPlan plan = planForBatch(ev, B);
@@ -1066,6 +1200,10 @@ int finishLoad(nsg_evaluator* ev, std::shared_ptr<NetWeights> W) {
     int rc;
     const int prec = ev->prec;
     const int es = nsg::elemSize(prec);
+    ev->G.reset();
+    ev->gAct.clear();
+    ev->gPlanes.release();
+    ev->loadedNodes = 0;
     ev->W = std::move(W);
     const NetWeights& N = *ev->W;
     ev->F = N.F; ev->blocks = N.blocks; ev->vc = N.vc; ev->vh = N.vh;
@@ -1164,6 +1302,44 @@ int finishLoad(nsg_evaluator* ev, std::shared_ptr<NetWeights> W) {
     ev->calibPending = false;
     ev->loaded = true;
     return NSG_OK;
+}
+
+// Load half of the general graph path: adopt the (possibly shared) plan and allocate this evaluator's activation
+// buffers for batchMax.
+int finishGraphLoad(nsg_evaluator* ev, std::shared_ptr<GraphWeights> G) {
+    int rc;
+    const nsg::graph::GraphPlan& P = *G->plan;
+    ev->loaded = false;
+    ev->W.reset();
+    ev->G = std::move(G);
+    ev->F = 0; ev->blocks = 0; ev->vc = 0; ev->vh = 0; ev->cpad = 0; ev->headsCout = 0; ev->fc1K = 0;
+    ev->params = P.params;
+    ev->trunkOut = nullptr;
+    ev->lastTrunkPrec = -1;
+    // (the specialised path's buffers of an earlier load are not used by a general graph)
+    ev->trunkLayerCount = 0;
+    ev->teamLayerCount = 0;
+    ev->coopEnabled = 0;
+    if ((rc = ev->gPlanes.alloc((size_t)ev->batchMax * 81 * P.planeStride * sizeof(float), true))) return rc;
+    ev->gAct.clear();
+    ev->gAct.resize(P.bufSpatialStride.size());
+    for (size_t i = 0; i < ev->gAct.size(); ++i)
+        if ((rc = ev->gAct[i].alloc(nsg::graph::bufferFloats(P, i, ev->batchMax) * sizeof(float), true))) return rc;
+    NSG_HIP(hipDeviceSynchronize());
+    ev->loaded = true;
+    return NSG_OK;
+}
+
+int uploadGraph(nsg_evaluator* ev, std::shared_ptr<const nsg::graph::GraphPlan> plan) {
+    int rc = bind(ev);
+    if (rc) return rc;
+    auto G = std::make_shared<GraphWeights>();
+    G->gpu = ev->gpu;
+    G->plan = std::move(plan);
+    const std::vector<float>& w = G->plan->weights;
+    if ((rc = G->w.alloc(w.size() * sizeof(float), false))) return rc;
+    if (!w.empty()) NSG_HIP(hipMemcpy(G->w.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+    return finishGraphLoad(ev, std::move(G));
 }
 
 int checkCompute(nsg_evaluator* ev, size_t n) {
@@ -1384,26 +1560,29 @@ int nsg_convert_onnx(const void* onnx, size_t size, void* dst, size_t capacity, 
 int nsg_load_memory(nsg_evaluator* ev, const void* blob, size_t size) {
     if (!ev || !blob) return fail(NSG_E_INVALID, "null argument");
     if (!nsg::onnx::isNsgw(blob, size)) { // what the engine passes: an ONNX model (trt.cc:121-131)
-        std::vector<unsigned char> converted;
-        std::string err;
-        if (!nsg::onnx::convertToNsgw(blob, size, &converted, &err))
-            return fail(NSG_E_FORMAT, "Failed to parse the model: neither an NSGW v1 weight file nor an ONNX model of the "
-                                      "supported topology (%s)", err.c_str());
-        return nsg_load_memory(ev, converted.data(), converted.size());
+        // the family matcher and the specialised loader first; what either refuses goes to the general graph planner
+        std::string famErr = "not tried (graph mode 1)";
+        if (ev->graphMode != NSG_GRAPH_FORCE) {
+            std::vector<unsigned char> converted;
+            if (nsg::onnx::convertToNsgw(blob, size, &converted, &famErr)) {
+                const int rc = nsg_load_memory(ev, converted.data(), converted.size());
+                if (rc == NSG_OK) ev->loadedNodes = nsg::graph::countNodes(blob, size);
+                if (rc != NSG_E_FORMAT) return rc;
+                famErr = gLastError;
+            }
+        }
+        auto plan = std::make_shared<nsg::graph::GraphPlan>();
+        std::string graphErr;
+        if (!nsg::graph::buildPlan(blob, size, ev->numChannels, plan.get(), &graphErr))
+            return fail(NSG_E_FORMAT, "Failed to parse the model: neither an NSGW v1 weight file nor an ONNX model that "
+                                      "loads (specialised path: %s; general graph path: %s)", famErr.c_str(), graphErr.c_str());
+        return uploadGraph(ev, std::move(plan));
     }
     int rc = bind(ev);
     if (rc) return rc;
     NetView nv;
     if ((rc = parseBlob(blob, size, &nv))) return rc;
-    if (nv.cin != ev->numChannels)
-        return fail(NSG_E_FORMAT, "weight file expects %d input planes, evaluator has %d", nv.cin,
-                    ev->numChannels);
-    // trt.cc:193-210: the policy output must have ml::MoveIndexMax elements
-    if (nv.pc * NSG_NUM_SQUARES != NSG_MOVE_INDEX_MAX)
-        return fail(NSG_E_FORMAT, "Unexpected PolicySize: %d (expected: %d).",
-                    nv.pc * NSG_NUM_SQUARES, NSG_MOVE_INDEX_MAX);
-    if (nv.F % 64 != 0) return fail(NSG_E_FORMAT, "trunk width %d is not a multiple of 64", nv.F);
-    if (nv.vh % 64 != 0) return fail(NSG_E_FORMAT, "value hidden width %d is not a multiple of 64", nv.vh);
+    if ((rc = checkSpecialised(nv, ev->numChannels))) return rc;
 
     const int prec = ev->prec;
     const int kc = nsg::inputChannelGranule(prec); // input channels are padded to whole chunks (kF16m8: chunk pairs)
@@ -1515,8 +1694,17 @@ int nsg_load_memory(nsg_evaluator* ev, const void* blob, size_t size) {
 // (hipMemcpyPeer over xGMI) per further device.
 int nsg_load_shared(nsg_evaluator* ev, nsg_evaluator* src) {
     if (!ev || !src) return fail(NSG_E_INVALID, "null argument");
-    if (!src->loaded || !src->W) return fail(NSG_E_NOT_LOADED, "the source evaluator has no weights loaded");
+    if (!src->loaded || (!src->W && !src->G)) return fail(NSG_E_NOT_LOADED, "the source evaluator has no weights loaded");
     if (ev == src) return NSG_OK;
+    if (src->G) { // a general graph: the same plan, shared on one device, uploaded again on another
+        if (ev->numChannels != src->G->plan->numChannels)
+            return fail(NSG_E_FORMAT, "network expects %d input planes, evaluator has %d", src->G->plan->numChannels, ev->numChannels);
+        if (ev->gpu == src->gpu) {
+            int rc = bind(ev);
+            return rc ? rc : finishGraphLoad(ev, src->G);
+        }
+        return uploadGraph(ev, src->G->plan);
+    }
     if (ev->prec != src->W->prec) return fail(NSG_E_INVALID, "precision differs from the source evaluator's");
     if (ev->numChannels != src->W->cin)
         return fail(NSG_E_FORMAT, "network expects %d input planes, evaluator has %d", src->W->cin, ev->numChannels);
@@ -1745,6 +1933,8 @@ int nsg_download_outputs(nsg_evaluator* ev, size_t batch_size, float* dst_policy
 int nsg_download_trunk(nsg_evaluator* ev, size_t batch_size, float* dst) {
     int rc = checkCompute(ev, batch_size);
     if (rc) return rc;
+    if (ev->G) return fail(NSG_E_INVALID, "%s: the loaded network runs on the general graph path, which has no trunk or "
+                                          "plane buffer of the specialised layout", "nsg_download_trunk");
     if (!ev->trunkOut) return fail(NSG_E_INVALID, "no forward has run yet");
     if ((rc = syncAndRecover(ev))) return rc;
     const size_t bytes = batch_size * ev->F * 81 * sizeof(float);
@@ -1759,6 +1949,8 @@ int nsg_download_trunk(nsg_evaluator* ev, size_t batch_size, float* dst) {
 int nsg_download_planes_raw(nsg_evaluator* ev, size_t batch_size, void* dst, size_t capacity, size_t* row_bytes) {
     int rc = checkCompute(ev, batch_size);
     if (rc) return rc;
+    if (ev->G) return fail(NSG_E_INVALID, "%s: the loaded network runs on the general graph path, which has no trunk or "
+                                          "plane buffer of the specialised layout", "nsg_download_planes_raw");
     if (!ev->trunkOut) return fail(NSG_E_INVALID, "no forward has run yet");
     if ((rc = syncAndRecover(ev))) return rc;
     if (ev->teamLast && ev->lastPersistent == 1)
@@ -1778,6 +1970,8 @@ int nsg_download_planes_raw(nsg_evaluator* ev, size_t batch_size, void* dst, siz
 int nsg_time_planes(nsg_evaluator* ev, size_t batch_size, int iterations, float* avg_ms, double* bytes_per_launch) {
     int rc = checkCompute(ev, batch_size);
     if (rc) return rc;
+    if (ev->G) return fail(NSG_E_INVALID, "%s: the loaded network runs on the general graph path, which has no trunk or "
+                                          "plane buffer of the specialised layout", "nsg_time_planes");
     if (iterations < 1 || !avg_ms) return fail(NSG_E_INVALID, "bad time_planes argument");
     if ((rc = syncAndRecover(ev))) return rc;
     const int prec = ev->prec;
@@ -1902,13 +2096,84 @@ int nsg_get_info(nsg_evaluator* ev, nsg_info* info) {
     info->clock_khz = ev->prop.clockRate;
     info->param_count = ev->params;
     const double F = ev->F, N = ev->blocks, C = ev->numChannels;
-    // stem + trunk + 1x1 policy (value/draw heads excluded)
-    info->flops_per_position = 2.0 * 81 * 9 * C * F + N * 2 * (2.0 * 81 * 9 * F * F) + 2.0 * 81 * 27 * F;
+    // stem + trunk + 1x1 policy (value/draw heads excluded); a general graph: every conv and dense layer
+    info->flops_per_position = ev->G ? ev->G->plan->flopsPerPosition
+                                     : 2.0 * 81 * 9 * C * F + N * 2 * (2.0 * 81 * 9 * F * F) + 2.0 * 81 * 27 * F;
     info->trunk_conv_flops_per_position = 2.0 * 81 * 9 * F * F;
     info->activation_bound_estimate = ev->W ? ev->W->actBound : 0.0;
     info->f16m8_window_fallback = (ev->W && ev->W->outsideM8Window) ? 1 : 0;
     // (boxes without the amdgpu.ids table report an empty marketing name: fall back to the ISA name)
     snprintf(info->device_name, sizeof(info->device_name), "%s", ev->prop.name[0] ? ev->prop.name : ev->prop.gcnArchName);
+    return NSG_OK;
+}
+
+int nsg_set_graph_mode(nsg_evaluator* ev, int mode) {
+    if (!ev) return fail(NSG_E_INVALID, "null evaluator");
+    if (ev->loaded) return fail(NSG_E_INVALID, "the graph mode must be chosen before nsg_load");
+    if (mode != NSG_GRAPH_AUTO && mode != NSG_GRAPH_FORCE) return fail(NSG_E_INVALID, "unknown graph mode %d", mode);
+    ev->graphMode = mode;
+    return NSG_OK;
+}
+
+static void graphInfoFromPlan(const nsg::graph::GraphPlan& P, nsg_graph_info* info) {
+    info->path = NSG_PATH_GRAPH;
+    info->precision = NSG_PRECISION_FP32;
+    info->nodes = P.nodes;
+    info->launches = (int)P.launches.size() + 2; // + plane expansion + output scatter
+    info->conv_launches = P.convLaunches;
+    info->param_count = P.params;
+    info->flops_per_position = P.flopsPerPosition;
+    info->activation_bytes_per_position = P.activationBytesPerPosition;
+}
+
+static void graphInfoFamily(const NetView& nv, int nodes, int prec, nsg_graph_info* info) {
+    info->path = NSG_PATH_SPECIALISED;
+    info->precision = prec;
+    info->nodes = nodes;
+    info->param_count = nv.params;
+    const double F = nv.F, N = nv.blocks, C = nv.cin;
+    info->flops_per_position = 2.0 * 81 * 9 * C * F + N * 2 * (2.0 * 81 * 9 * F * F) + 2.0 * 81 * 27 * F;
+}
+
+int nsg_get_graph_info(nsg_evaluator* ev, nsg_graph_info* info) {
+    if (!ev || !info) return fail(NSG_E_INVALID, "null argument");
+    if (!ev->loaded) return fail(NSG_E_NOT_LOADED, "no network loaded");
+    memset(info, 0, sizeof(*info));
+    if (ev->G) {
+        graphInfoFromPlan(*ev->G->plan, info);
+        info->activation_bytes = ev->gPlanes.bytes;
+        for (const DevBuf& b : ev->gAct) info->activation_bytes += b.bytes;
+        return NSG_OK;
+    }
+    info->path = NSG_PATH_SPECIALISED;
+    info->precision = ev->prec;
+    info->nodes = ev->loadedNodes;
+    info->param_count = ev->params;
+    const double F = ev->F, N = ev->blocks, C = ev->numChannels;
+    info->flops_per_position = 2.0 * 81 * 9 * C * F + N * 2 * (2.0 * 81 * 9 * F * F) + 2.0 * 81 * 27 * F;
+    return NSG_OK;
+}
+
+int nsg_inspect_onnx(const void* onnx, size_t size, int num_channels, nsg_graph_info* info) {
+    if (!onnx || !info || num_channels <= 0) return fail(NSG_E_INVALID, "bad argument");
+    memset(info, 0, sizeof(*info));
+    std::string famErr;
+    std::vector<unsigned char> converted;
+    if (nsg::onnx::convertToNsgw(onnx, size, &converted, &famErr)) {
+        NetView nv;
+        int rc = parseBlob(converted.data(), converted.size(), &nv);
+        if (rc == NSG_OK && (rc = checkSpecialised(nv, num_channels)) == NSG_OK) {
+            graphInfoFamily(nv, nsg::graph::countNodes(onnx, size), NSG_PRECISION_FP32, info);
+            return NSG_OK;
+        }
+        famErr = gLastError;
+    }
+    nsg::graph::GraphPlan plan;
+    std::string graphErr;
+    if (!nsg::graph::buildPlan(onnx, size, num_channels, &plan, &graphErr))
+        return fail(NSG_E_FORMAT, "Failed to parse the model: neither an NSGW v1 weight file nor an ONNX model that "
+                                  "loads (specialised path: %s; general graph path: %s)", famErr.c_str(), graphErr.c_str());
+    graphInfoFromPlan(plan, info);
     return NSG_OK;
 }
 

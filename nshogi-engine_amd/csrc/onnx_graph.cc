@@ -1,0 +1,1132 @@
+// onnx_graph.cc -- see onnx_graph.h and DESIGN.md section 13.
+#include "onnx_graph.h"
+#include "onnx_proto.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <set>
+
+namespace nsg {
+namespace graph {
+
+namespace {
+
+using namespace nsg::onnx::wire;
+
+constexpr int64_t kBatch = INT64_MIN / 2; // the symbolic batch dimension inside folded shape values
+constexpr int kNoRes = -2;
+constexpr int kPending = -3; // the view of an open elementwise group: its buffer is assigned when the group is emitted
+
+int roundUp(int a, int b) { return (a + b - 1) / b * b; }
+
+std::string dimsStr(const std::vector<int64_t>& D) {
+    std::string S = "[";
+    for (size_t I = 0; I < D.size(); ++I) {
+        if (I) S += ",";
+        S += D[I] == kBatch ? std::string("N") : std::to_string(D[I]);
+    }
+    return S + "]";
+}
+
+// A tensor of the graph: a host value (constant or folded shape), or a runtime tensor on the device.
+struct Val {
+    bool runtime = false;
+    std::vector<int64_t> dims; // runtime: logical ONNX dims, dims[0] = kBatch
+    // host
+    bool isInt = false;
+    std::vector<double> f;
+    std::vector<int64_t> i;
+    // runtime
+    View v;
+    bool flatOfSpatial = false; // a flattened spatial tensor [N, C*81] (index c*81 + square); v is the spatial view
+    int group = -1;             // open elementwise group that computes it (v not yet assigned)
+    std::string producer;       // node name
+    size_t count() const { return isInt ? i.size() : f.size(); }
+    double at(size_t k) const { return isInt ? (double)i[k] : f[k]; }
+};
+
+// An elementwise chain being fused into one launch.
+struct Group {
+    bool open = true;
+    bool spatial = false;
+    int C = 0;
+    std::vector<EltSrc> srcs;
+    std::vector<EltInstr> code;
+    int nregs = 0;
+    int outReg = 0;
+    std::string out;  // tensor it computes
+    std::string name; // nodes
+};
+
+class Planner {
+ public:
+    Planner(const Graph& G, int NumChannels, GraphPlan* P) : G(G), P(*P), NumChannels(NumChannels) {}
+
+    void run();
+
+ private:
+    const Graph& G;
+    GraphPlan& P;
+    const int NumChannels;
+    std::map<std::string, Val> Vals;
+    std::map<std::string, int> Uses; // live consumers (+1 for a graph output)
+    std::set<std::string> Outputs;
+    std::vector<bool> Skip;          // nodes absorbed into an earlier launch
+    std::vector<Node> Nodes;         // after the swish rewrite
+    std::vector<Group> Groups;
+    std::vector<int> VirtStride;     // per produced tensor (virtual buffer)
+    std::vector<bool> VirtSpatial;
+
+    [[noreturn]] void fail(const Node& N, const std::string& Why) const {
+        throw Error("node '" + N.Name + "' (" + N.Op + "): " + Why);
+    }
+    const Val& get(const Node& N, size_t Idx) {
+        if (Idx >= N.In.size() || N.In[Idx].empty()) fail(N, "missing input " + std::to_string(Idx));
+        auto It = Vals.find(N.In[Idx]);
+        if (It == Vals.end()) fail(N, "input '" + N.In[Idx] + "' is not defined before its use");
+        return It->second;
+    }
+    bool has(const Node& N, size_t Idx) const { return Idx < N.In.size() && !N.In[Idx].empty(); }
+    const Val& host(const Node& N, size_t Idx, const char* What) {
+        const Val& V = get(N, Idx);
+        if (V.runtime) fail(N, std::string(What) + " must be a constant (it is computed at run time)");
+        return V;
+    }
+    std::vector<int64_t> ints(const Node& N, size_t Idx, const char* What) {
+        const Val& V = host(N, Idx, What);
+        std::vector<int64_t> R;
+        for (size_t K = 0; K < V.count(); ++K) R.push_back(V.isInt ? V.i[K] : (int64_t)V.f[K]);
+        return R;
+    }
+    int newVirt(int Stride, bool Spatial) {
+        VirtStride.push_back(Stride);
+        VirtSpatial.push_back(Spatial);
+        return (int)VirtStride.size() - 1;
+    }
+    View freshView(int C, bool Spatial) {
+        View V;
+        V.stride = roundUp(std::max(C, 1), kChunk);
+        V.C = C;
+        V.spatial = Spatial;
+        V.buf = newVirt(V.stride, Spatial);
+        return V;
+    }
+    size_t addConst(const std::vector<float>& F) {
+        const size_t Off = P.weights.size();
+        P.weights.insert(P.weights.end(), F.begin(), F.end());
+        while (P.weights.size() % 4) P.weights.push_back(0.f); // every record 16-byte aligned
+        return Off;
+    }
+
+    // runtime tensor kinds
+    static bool isSpatialDims(const std::vector<int64_t>& D) {
+        return D.size() == 4 && D[0] == kBatch && D[1] > 0 && D[2] == 9 && D[3] == 9;
+    }
+    // flat: [N], [N,C], [N,C,1], [N,C,1,1]; returns C or -1
+    static int flatC(const std::vector<int64_t>& D) {
+        if (D.empty() || D.size() > 4 || D[0] != kBatch) return -1;
+        if (D.size() == 1) return 1;
+        if (D[1] <= 0) return -1;
+        for (size_t K = 2; K < D.size(); ++K)
+            if (D[K] != 1) return -1;
+        return (int)D[1];
+    }
+    Val runtimeVal(const Node& N, const std::vector<int64_t>& Dims) const {
+        Val V;
+        V.runtime = true;
+        V.dims = Dims;
+        V.producer = N.Name;
+        if (!isSpatialDims(Dims) && flatC(Dims) < 0)
+            fail(N, "output shape " + dimsStr(Dims) + " is neither [N,C,9,9] nor flat [N,C] / [N,C,1,1]");
+        return V;
+    }
+
+    void emit(Launch L) {
+        if (L.kind == kLaunchConv) ++P.convLaunches;
+        P.launches.push_back(std::move(L));
+    }
+    void emitGroup(int Gi) {
+        Group& Gr = Groups[(size_t)Gi];
+        if (!Gr.open) return;
+        Gr.open = false;
+        Launch L;
+        L.kind = kLaunchElt;
+        L.name = Gr.name;
+        L.out = freshView(Gr.C, Gr.spatial);
+        L.srcs = Gr.srcs;
+        L.code = Gr.code;
+        L.eltOut = Gr.outReg;
+        emit(L);
+        Val& V = Vals[Gr.out];
+        V.v = L.out;
+        V.group = -1;
+    }
+    // the value's device view, every pending launch that computes it emitted
+    const Val& ready(const std::string& Name) {
+        Val& V = Vals.at(Name);
+        if (V.group >= 0) emitGroup(V.group);
+        return Vals.at(Name);
+    }
+    // a view with offset 0 in a buffer of its own kind (conv input, dense input, mean input)
+    View plain(const std::string& Name, const std::string& Why) {
+        const Val& V0 = ready(Name);
+        if (!V0.flatOfSpatial && V0.v.offset == 0 && V0.v.stride == roundUp(V0.v.C, kChunk)) return V0.v;
+        Launch L;
+        L.name = Why;
+        if (V0.flatOfSpatial) {
+            L.kind = kLaunchFlatten;
+            L.in = V0.v;
+            L.out = freshView(V0.v.C * 81, false);
+        } else {
+            L.kind = kLaunchConcat;
+            CopySeg S;
+            S.v = V0.v;
+            L.segs.push_back(S);
+            L.out = freshView(V0.v.C, V0.v.spatial);
+        }
+        const View Out = L.out;
+        emit(L);
+        Val& V = Vals[Name];
+        V.v = Out;
+        V.flatOfSpatial = false;
+        return Out;
+    }
+
+    void hostFold(const Node& N);
+    void linear(const Node& N, size_t Index);
+    void elementwise(const Node& N);
+    void checkOutputs();
+    void assignBuffers();
+    bool absorbable(const std::string& T) const {
+        auto It = Uses.find(T);
+        return !Outputs.count(T) && It != Uses.end() && It->second == 1;
+    }
+    const Node* onlyConsumer(const std::string& T, size_t After) const {
+        for (size_t K = After + 1; K < Nodes.size(); ++K) {
+            if (Skip[K]) continue;
+            for (const std::string& I : Nodes[K].In)
+                if (I == T) return &Nodes[K];
+        }
+        return nullptr;
+    }
+    size_t indexOf(const Node* N) const { return (size_t)(N - Nodes.data()); }
+};
+
+bool isAct(const std::string& Op) {
+    return Op == "Relu" || Op == "Sigmoid" || Op == "Tanh" || Op == "Softplus" || Op == "Swish";
+}
+int actOf(const std::string& Op) {
+    if (Op == "Relu") return kActRelu;
+    if (Op == "Sigmoid") return kActSigmoid;
+    if (Op == "Tanh") return kActTanh;
+    if (Op == "Softplus") return kActSoftplus;
+    if (Op == "Swish") return kActSwish;
+    return kActNone;
+}
+bool isBinary(const std::string& Op) { return Op == "Add" || Op == "Sub" || Op == "Mul" || Op == "Div"; }
+
+const std::set<std::string>& opSet() {
+    static const std::set<std::string> S = {
+        "Conv", "BatchNormalization", "Relu", "Sigmoid", "Tanh", "Softplus", "Add", "Sub", "Mul", "Div",
+        "GlobalAveragePool", "ReduceMean", "Flatten", "Reshape", "Squeeze", "Unsqueeze", "Gemm", "MatMul",
+        "Concat", "Slice", "Identity", "Constant",
+        // folded on the host only (shape chains): refused on a runtime tensor
+        "Shape", "Gather", "Cast"};
+    return S;
+}
+
+// NumPy broadcast of two shapes (batch symbolic)
+bool broadcast(const std::vector<int64_t>& A, const std::vector<int64_t>& B, std::vector<int64_t>* Out) {
+    const size_t R = std::max(A.size(), B.size());
+    Out->assign(R, 1);
+    for (size_t K = 0; K < R; ++K) {
+        const int64_t X = K < R - A.size() ? 1 : A[K - (R - A.size())];
+        const int64_t Y = K < R - B.size() ? 1 : B[K - (R - B.size())];
+        if (X == Y || Y == 1) (*Out)[K] = X;
+        else if (X == 1) (*Out)[K] = Y;
+        else return false;
+    }
+    return true;
+}
+
+// axes along which a shape, right-aligned to an output of rank R, varies (size != 1)
+std::vector<int> variesAlong(const std::vector<int64_t>& D, size_t R) {
+    std::vector<int> Ax;
+    for (size_t K = 0; K < D.size(); ++K)
+        if (D[K] != 1) Ax.push_back((int)(K + R - D.size()));
+    return Ax;
+}
+
+// ---- host folding (constants and shape chains) ---------------------------------------------------------------
+void Planner::hostFold(const Node& N) {
+    const std::string& Op = N.Op;
+    Val R;
+    auto Out = [&]() -> Val& { return Vals[N.Out[0]]; };
+    if (Op == "Shape") {
+        const Val& X = get(N, 0);
+        std::vector<int64_t> D = X.dims;
+        if (X.runtime && X.flatOfSpatial) D = {kBatch, (int64_t)X.v.C * 81};
+        int64_t S = N.attrI("start", 0), E = N.attrI("end", (int64_t)D.size());
+        if (S < 0) S += (int64_t)D.size();
+        if (E < 0) E += (int64_t)D.size();
+        S = std::max<int64_t>(0, std::min<int64_t>(S, (int64_t)D.size()));
+        E = std::max<int64_t>(S, std::min<int64_t>(E, (int64_t)D.size()));
+        R.isInt = true;
+        R.i.assign(D.begin() + S, D.begin() + E);
+        R.dims = {E - S};
+        Out() = R;
+        return;
+    }
+    if (Op == "Identity") { Out() = get(N, 0); return; }
+    const Val& X = host(N, 0, "the data input");
+    if (Op == "Cast") {
+        const int64_t To = N.attrI("to", 1);
+        R.dims = X.dims;
+        if (To == 7 || To == 6) {
+            R.isInt = true;
+            for (size_t K = 0; K < X.count(); ++K) R.i.push_back(X.isInt ? X.i[K] : (int64_t)X.f[K]);
+        } else if (To == 1 || To == 11) {
+            for (size_t K = 0; K < X.count(); ++K) {
+                if (X.isInt && X.i[K] == kBatch) fail(N, "cannot cast the batch dimension to a float");
+                R.f.push_back(X.at(K));
+            }
+        } else {
+            fail(N, "Cast to data type " + std::to_string(To) + " is not supported");
+        }
+        Out() = R;
+        return;
+    }
+    if (Op == "Gather") {
+        const std::vector<int64_t> Idx = ints(N, 1, "Gather's indices");
+        const Val& Iv = host(N, 1, "Gather's indices");
+        if (X.dims.size() != 1 || N.attrI("axis", 0) != 0) fail(N, "Gather is folded only on a 1-D constant along axis 0");
+        R.isInt = X.isInt;
+        for (int64_t K : Idx) {
+            const int64_t J = K < 0 ? K + (int64_t)X.count() : K;
+            if (J < 0 || J >= (int64_t)X.count()) fail(N, "Gather index out of range");
+            if (X.isInt) R.i.push_back(X.i[(size_t)J]);
+            else R.f.push_back(X.f[(size_t)J]);
+        }
+        R.dims = Iv.dims;
+        Out() = R;
+        return;
+    }
+    if (Op == "Unsqueeze" || Op == "Squeeze") {
+        std::vector<int64_t> Axes = has(N, 1) ? ints(N, 1, "axes") : N.attrInts("axes", {});
+        R = X;
+        std::vector<int64_t> D = X.dims;
+        if (Op == "Unsqueeze") {
+            const int64_t Rank = (int64_t)(D.size() + Axes.size());
+            for (int64_t& A : Axes) if (A < 0) A += Rank;
+            std::sort(Axes.begin(), Axes.end());
+            for (int64_t A : Axes) {
+                if (A < 0 || A > (int64_t)D.size()) fail(N, "axis out of range");
+                D.insert(D.begin() + A, 1);
+            }
+        } else {
+            std::vector<int64_t> ND;
+            for (size_t K = 0; K < D.size(); ++K) {
+                bool Drop = Axes.empty() ? D[K] == 1 : false;
+                for (int64_t A : Axes) Drop = Drop || (A < 0 ? A + (int64_t)D.size() : A) == (int64_t)K;
+                if (!Drop) ND.push_back(D[K]);
+            }
+            D = ND;
+        }
+        R.dims = D;
+        Out() = R;
+        return;
+    }
+    if (Op == "Concat") {
+        R.isInt = X.isInt;
+        int64_t Total = 0;
+        for (size_t K = 0; K < N.In.size(); ++K) {
+            const Val& V = host(N, K, "a Concat input");
+            if (V.dims.size() != 1) fail(N, "Concat of constants is folded only for 1-D values");
+            if (V.isInt != R.isInt) fail(N, "Concat of mixed data types");
+            R.i.insert(R.i.end(), V.i.begin(), V.i.end());
+            R.f.insert(R.f.end(), V.f.begin(), V.f.end());
+            Total += V.dims[0];
+        }
+        R.dims = {Total};
+        Out() = R;
+        return;
+    }
+    if (Op == "Slice") {
+        if (X.dims.size() != 1) fail(N, "Slice of a constant is folded only for 1-D values");
+        const std::vector<int64_t> St = ints(N, 1, "starts"), En = ints(N, 2, "ends");
+        const std::vector<int64_t> Sp = has(N, 4) ? ints(N, 4, "steps") : std::vector<int64_t>{1};
+        if (St.size() != 1 || En.size() != 1 || Sp.size() != 1 || Sp[0] != 1) fail(N, "only a unit-step 1-D slice is folded");
+        const int64_t Len = (int64_t)X.count();
+        int64_t S = St[0] < 0 ? St[0] + Len : St[0], E = En[0] < 0 ? En[0] + Len : En[0];
+        S = std::max<int64_t>(0, std::min(S, Len));
+        E = std::max<int64_t>(S, std::min(E, Len));
+        R.isInt = X.isInt;
+        for (int64_t K = S; K < E; ++K) {
+            if (X.isInt) R.i.push_back(X.i[(size_t)K]);
+            else R.f.push_back(X.f[(size_t)K]);
+        }
+        R.dims = {E - S};
+        Out() = R;
+        return;
+    }
+    if (Op == "Reshape") {
+        const std::vector<int64_t> Sh = ints(N, 1, "the target shape");
+        R = X;
+        int64_t Known = 1, Infer = -1;
+        for (size_t K = 0; K < Sh.size(); ++K) {
+            if (Sh[K] == -1) Infer = (int64_t)K;
+            else if (Sh[K] == 0 && K < X.dims.size()) Known *= X.dims[K];
+            else Known *= Sh[K];
+        }
+        R.dims = Sh;
+        for (size_t K = 0; K < Sh.size(); ++K)
+            if (Sh[K] == 0 && K < X.dims.size()) R.dims[K] = X.dims[K];
+        if (Infer >= 0) R.dims[(size_t)Infer] = Known ? (int64_t)X.count() / Known : 0;
+        Out() = R;
+        return;
+    }
+    if (isBinary(Op)) {
+        const Val& Y = host(N, 1, "the second operand");
+        std::vector<int64_t> D;
+        if (!broadcast(X.dims, Y.dims, &D)) fail(N, "shapes " + dimsStr(X.dims) + " and " + dimsStr(Y.dims) + " do not broadcast");
+        const size_t Cnt = std::max(X.count(), Y.count());
+        if ((X.count() != Cnt && X.count() != 1) || (Y.count() != Cnt && Y.count() != 1))
+            fail(N, "constant folding supports equal shapes or a scalar operand");
+        R.dims = D;
+        R.isInt = X.isInt && Y.isInt;
+        for (size_t K = 0; K < Cnt; ++K) {
+            const size_t A = X.count() == 1 ? 0 : K, B = Y.count() == 1 ? 0 : K;
+            if (R.isInt) {
+                const int64_t P1 = X.i[A], P2 = Y.i[B];
+                int64_t V;
+                const bool Sym = P1 == kBatch || P2 == kBatch;
+                if (Sym) {
+                    const int64_t Other = P1 == kBatch ? P2 : P1;
+                    const bool Neutral = ((Op == "Mul") && Other == 1) || ((Op == "Div") && P1 == kBatch && Other == 1) ||
+                                         ((Op == "Add" || Op == "Sub") && Other == 0 && !(Op == "Sub" && P2 == kBatch));
+                    if (!Neutral || (P1 == kBatch && P2 == kBatch)) fail(N, "arithmetic on the symbolic batch dimension");
+                    V = kBatch;
+                } else if (Op == "Add") V = P1 + P2;
+                else if (Op == "Sub") V = P1 - P2;
+                else if (Op == "Mul") V = P1 * P2;
+                else {
+                    if (P2 == 0) fail(N, "integer division by zero");
+                    V = P1 / P2;
+                }
+                R.i.push_back(V);
+            } else {
+                if ((X.isInt && X.i[A] == kBatch) || (Y.isInt && Y.i[B] == kBatch)) fail(N, "arithmetic on the symbolic batch dimension");
+                const double P1 = X.at(A), P2 = Y.at(B);
+                R.f.push_back(Op == "Add" ? P1 + P2 : Op == "Sub" ? P1 - P2 : Op == "Mul" ? P1 * P2 : P1 / P2);
+            }
+        }
+        Out() = R;
+        return;
+    }
+    fail(N, "is applied to constants only; folding it is not supported");
+}
+
+// ---- Conv / Gemm / MatMul with their epilogue --------------------------------------------------------------------
+void Planner::linear(const Node& N, size_t Index) {
+    const Val& X = get(N, 0);
+    if (!X.runtime) fail(N, "the data input is a constant");
+    const bool Dense = N.Op != "Conv";
+    int Cin = 0, Cout = 0, K = 1;
+    std::vector<double> W, Bias; // W[cout][cin][taps]
+    std::string Name = N.Name;
+    if (!Dense) {
+        const Val& Wt = host(N, 1, "the weight");
+        if (Wt.isInt || Wt.dims.size() != 4 || Wt.dims[2] != Wt.dims[3] || (Wt.dims[2] != 1 && Wt.dims[2] != 3))
+            fail(N, "only 1x1 and 3x3 float weights");
+        K = (int)Wt.dims[2];
+        const int64_t Pad = K / 2;
+        bool Ok = N.attrI("group", 1) == 1;
+        for (int64_t S : N.attrInts("strides", {1, 1})) Ok = Ok && S == 1;
+        for (int64_t D : N.attrInts("dilations", {1, 1})) Ok = Ok && D == 1;
+        const std::vector<int64_t> Pads = N.attrInts("pads", {0, 0, 0, 0});
+        Ok = Ok && Pads.size() == 4;
+        for (int64_t P1 : Pads) Ok = Ok && P1 == Pad;
+        if (N.Attrs.count("auto_pad")) Ok = false;
+        if (!Ok) fail(N, "only stride 1, dilation 1, group 1 and 'same' padding (explicit pads)");
+        Cout = (int)Wt.dims[0];
+        Cin = (int)Wt.dims[1];
+        if (X.flatOfSpatial || !isSpatialDims(X.dims)) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
+        if ((int)X.dims[1] != Cin)
+            fail(N, "the weight expects " + std::to_string(Cin) + " input channels, '" + N.In[0] + "' has " + std::to_string(X.dims[1]));
+        W.assign(Wt.f.begin(), Wt.f.end());
+        Bias.assign((size_t)Cout, 0.0);
+        if (has(N, 2)) {
+            const Val& B = host(N, 2, "the bias");
+            if ((int)B.count() != Cout) fail(N, "bias length does not match the output channels");
+            for (int C = 0; C < Cout; ++C) Bias[(size_t)C] = B.at((size_t)C);
+        }
+    } else {
+        const Val& Wt = host(N, 1, "the weight");
+        if (Wt.isInt || Wt.dims.size() != 2) fail(N, "expected a 2-D float weight");
+        bool TransB = false;
+        if (N.Op == "Gemm") {
+            if (N.attrF("alpha", 1.0) != 1.0 || N.attrF("beta", 1.0) != 1.0 || N.attrI("transA", 0) != 0)
+                fail(N, "Gemm with alpha = beta = 1, transA = 0 only");
+            TransB = N.attrI("transB", 0) != 0;
+        }
+        Cout = (int)(TransB ? Wt.dims[0] : Wt.dims[1]);
+        Cin = (int)(TransB ? Wt.dims[1] : Wt.dims[0]);
+        const int XC = X.flatOfSpatial ? X.v.C * 81 : flatC(X.dims);
+        if (X.dims.size() != 2 && !X.flatOfSpatial) fail(N, "input " + dimsStr(X.dims) + " is not 2-D [N,K]");
+        if (XC != Cin) fail(N, "the weight expects K = " + std::to_string(Cin) + ", '" + N.In[0] + "' has " + std::to_string(XC));
+        W.assign((size_t)Cout * Cin, 0.0);
+        for (int O = 0; O < Cout; ++O)
+            for (int I = 0; I < Cin; ++I)
+                W[(size_t)O * Cin + I] = TransB ? Wt.f[(size_t)O * Cin + I] : Wt.f[(size_t)I * Cout + O];
+        Bias.assign((size_t)Cout, 0.0);
+        if (N.Op == "Gemm" && has(N, 2)) {
+            const Val& B = host(N, 2, "the bias");
+            if ((int)B.count() != Cout && B.count() != 1) fail(N, "bias length does not match");
+            for (int C = 0; C < Cout; ++C) Bias[(size_t)C] = B.at(B.count() == 1 ? 0 : (size_t)C);
+        }
+    }
+    const int Taps = K * K;
+    std::vector<int64_t> Dims = Dense ? std::vector<int64_t>{kBatch, Cout} : std::vector<int64_t>{kBatch, Cout, 9, 9};
+    // epilogue: [BatchNorm | constant per-channel Add]*  [+ runtime residual]  [activation]
+    std::string Cur = N.Out[0];
+    std::string Res;
+    int Act = kActNone;
+    size_t At = Index;
+    while (absorbable(Cur)) {
+        const Node* C = onlyConsumer(Cur, At);
+        if (!C) break;
+        if (C->Op == "BatchNormalization" && Res.empty() && Act == kActNone && C->In.size() >= 5 && C->In[0] == Cur) {
+            bool Const = true;
+            for (size_t S = 1; S < 5; ++S) Const = Const && Vals.count(C->In[S]) && !Vals.at(C->In[S]).runtime && Vals.at(C->In[S]).count() == (size_t)Cout;
+            if (!Const) break;
+            const double Eps = C->attrF("epsilon", 1e-5);
+            for (int O = 0; O < Cout; ++O) {
+                const double Gm = Vals.at(C->In[1]).at((size_t)O), Bt = Vals.at(C->In[2]).at((size_t)O);
+                const double Mn = Vals.at(C->In[3]).at((size_t)O), Vr = Vals.at(C->In[4]).at((size_t)O);
+                const double S = Gm / std::sqrt(Vr + Eps);
+                for (size_t J = (size_t)O * Cin * Taps; J < (size_t)(O + 1) * Cin * Taps; ++J) W[J] *= S;
+                Bias[(size_t)O] = (Bias[(size_t)O] - Mn) * S + Bt;
+            }
+        } else if (C->Op == "Add" && C->In.size() == 2) {
+            const std::string& Other = C->In[0] == Cur ? C->In[1] : C->In[0];
+            auto It = Vals.find(Other);
+            if (It == Vals.end() || Other == Cur) break;
+            const Val& O = It->second;
+            if (!O.runtime) { // a per-channel constant: the bias
+                if (!Res.empty() || Act != kActNone) break;
+                std::vector<int64_t> BD;
+                if (!broadcast(Dims, O.dims, &BD) || BD != Dims) break;
+                const std::vector<int> Ax = variesAlong(O.dims, Dims.size());
+                if (!(Ax.empty() || (Ax.size() == 1 && Ax[0] == 1))) break;
+                for (int Ch = 0; Ch < Cout; ++Ch) Bias[(size_t)Ch] += O.at(Ax.empty() ? 0 : (size_t)Ch);
+            } else {
+                if (!Res.empty() || Act != kActNone || O.flatOfSpatial || O.dims != Dims) break;
+                Res = Other;
+            }
+        } else if (isAct(C->Op) && Act == kActNone && C->In[0] == Cur) {
+            Act = actOf(C->Op);
+        } else {
+            break;
+        }
+        Name += "+" + C->Name;
+        Skip[indexOf(C)] = true;
+        At = indexOf(C);
+        Cur = C->Out[0];
+        if (Act != kActNone) break;
+    }
+    Launch L;
+    L.kind = kLaunchConv;
+    L.name = Name;
+    L.dense = Dense;
+    L.taps = Taps;
+    L.in = plain(N.In[0], N.Name + " (input copy)");
+    L.cinPad = roundUp(Cin, kChunk);
+    L.coutTiles = (Cout + kCoutTile - 1) / kCoutTile;
+    L.act = Act;
+    L.res.buf = kNoRes;
+    if (!Res.empty()) L.res = ready(Res).v;
+    {   // packed [tile][chunk][tap][16][64], f32 of the double product (BatchNorm folded in double)
+        const int Chunks = L.cinPad / kChunk;
+        std::vector<float> Pk((size_t)L.coutTiles * Chunks * Taps * kChunk * kCoutTile, 0.f);
+        for (int T = 0; T < L.coutTiles; ++T)
+            for (int Ch = 0; Ch < Chunks; ++Ch)
+                for (int Tp = 0; Tp < Taps; ++Tp)
+                    for (int Kk = 0; Kk < kChunk; ++Kk)
+                        for (int Nn = 0; Nn < kCoutTile; ++Nn) {
+                            const int O = T * kCoutTile + Nn, I = Ch * kChunk + Kk;
+                            if (O >= Cout || I >= Cin) continue;
+                            Pk[((((size_t)T * Chunks + Ch) * Taps + Tp) * kChunk + Kk) * kCoutTile + Nn] =
+                                (float)W[((size_t)O * Cin + I) * Taps + Tp];
+                        }
+        L.wOff = addConst(Pk);
+        std::vector<float> Bf((size_t)L.coutTiles * kCoutTile, 0.f);
+        for (int O = 0; O < Cout; ++O) Bf[(size_t)O] = (float)Bias[(size_t)O];
+        L.biasOff = addConst(Bf);
+    }
+    L.out = freshView(Cout, !Dense);
+    P.flopsPerPosition += 2.0 * (Dense ? 1 : 81) * Taps * (double)Cin * Cout;
+    Val V = runtimeVal(N, Dims);
+    V.v = L.out;
+    V.producer = N.Name;
+    emit(L);
+    Vals[Cur] = V;
+}
+
+// ---- elementwise ops: fused into groups ------------------------------------------------------------------------
+void Planner::elementwise(const Node& N) {
+    std::vector<std::vector<int64_t>> InDims;
+    std::vector<int64_t> D;
+    const size_t Arity = isBinary(N.Op) ? 2 : 1;
+    for (size_t K = 0; K < Arity; ++K) {
+        const Val& V = get(N, K);
+        std::vector<int64_t> Di = V.runtime && V.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)V.v.C * 81} : V.dims;
+        std::vector<int64_t> Bd;
+        if (K == 0) D = Di;
+        else if (!broadcast(D, Di, &Bd)) fail(N, "shapes " + dimsStr(D) + " and " + dimsStr(Di) + " do not broadcast");
+        else D = Bd;
+        InDims.push_back(Di);
+    }
+    const bool Spatial = isSpatialDims(D);
+    const int C = Spatial ? (int)D[1] : flatC(D);
+    if (C < 0) fail(N, "output shape " + dimsStr(D) + " is neither [N,C,9,9] nor flat");
+    Group NG;
+    NG.spatial = Spatial;
+    NG.C = C;
+    NG.name = N.Name;
+    NG.out = N.Out[0];
+    // operand -> register
+    auto operand = [&](size_t K) -> int {
+        const std::string& Name = N.In[K];
+        Val& V = Vals.at(Name);
+        if (!V.runtime) {
+            const std::vector<int> Ax = variesAlong(InDims[K], D.size());
+            EltSrc S;
+            if (Ax.empty()) {
+                if (V.count() < 1) fail(N, "empty constant");
+                S.mode = kSrcScalar;
+                S.scalar = (float)V.at(0);
+            } else if (Ax.size() == 1 && Ax[0] == 1 && D.size() >= 2) {
+                std::vector<float> F((size_t)C);
+                for (int Ch = 0; Ch < C; ++Ch) F[(size_t)Ch] = (float)V.at((size_t)Ch);
+                S.mode = kSrcChannel;
+                S.constOff = addConst(F);
+            } else {
+                fail(N, "constant of shape " + dimsStr(InDims[K]) + " broadcast to " + dimsStr(D) + " (per-channel and scalar constants only)");
+            }
+            if (NG.srcs.size() >= (size_t)kMaxEltSrcs) fail(N, "too many inputs for one fused launch");
+            NG.srcs.push_back(S);
+            const int R = NG.nregs++;
+            NG.code.push_back(EltInstr{kEltLoad, (uint8_t)R, (uint8_t)(NG.srcs.size() - 1), 0});
+            return R;
+        }
+        // runtime operand: how it varies relative to the output
+        const std::vector<int64_t>& Di = InDims[K];
+        const bool Same = Di == D || (flatC(Di) == C && !Spatial && flatC(D) == C);
+        const bool Board = Spatial && !V.flatOfSpatial && flatC(Di) == C && Di.size() == 4;
+        if (!Same && !Board) fail(N, "operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
+        // an open group used only here: inline its program
+        const Group* Open = V.group >= 0 ? &Groups[(size_t)V.group] : nullptr;
+        const bool Domain = Open && !V.flatOfSpatial && Open->C == C &&
+                            (Open->spatial == Spatial || (Board && !Open->spatial));
+        if (Domain && absorbable(Name)) {
+            Group& Gr = Groups[(size_t)V.group];
+            if (NG.srcs.size() + Gr.srcs.size() <= (size_t)kMaxEltSrcs && NG.code.size() + Gr.code.size() + 2 <= (size_t)kMaxEltCode &&
+                NG.nregs + Gr.nregs + 1 <= kMaxEltRegs) {
+                const int RB = NG.nregs, SB = (int)NG.srcs.size();
+                for (EltSrc S : Gr.srcs) {
+                    if (Board && S.mode == kSrcSame) S.mode = kSrcBoard;
+                    NG.srcs.push_back(S);
+                }
+                for (EltInstr I : Gr.code) {
+                    I.dst = (uint8_t)(I.dst + RB);
+                    if (I.op == kEltLoad) I.a = (uint8_t)(I.a + SB);
+                    else {
+                        I.a = (uint8_t)(I.a + RB);
+                        if (I.op != kEltAct) I.b = (uint8_t)(I.b + RB);
+                    }
+                    NG.code.push_back(I);
+                }
+                NG.nregs += Gr.nregs;
+                NG.name = Gr.name + "+" + NG.name;
+                Gr.open = false;
+                V.group = -1;
+                return RB + Gr.outReg;
+            }
+        }
+        const View Vw = V.flatOfSpatial ? plain(Name, N.Name + " (flatten)") : ready(Name).v;
+        if (NG.srcs.size() >= (size_t)kMaxEltSrcs) fail(N, "too many inputs for one fused launch");
+        EltSrc S;
+        S.mode = Board ? kSrcBoard : kSrcSame;
+        S.v = Vw;
+        NG.srcs.push_back(S);
+        const int R = NG.nregs++;
+        NG.code.push_back(EltInstr{kEltLoad, (uint8_t)R, (uint8_t)(NG.srcs.size() - 1), 0});
+        return R;
+    };
+    int Out;
+    if (isAct(N.Op)) {
+        const int A = operand(0);
+        Out = NG.nregs++;
+        NG.code.push_back(EltInstr{kEltAct, (uint8_t)Out, (uint8_t)A, (uint8_t)actOf(N.Op)});
+    } else if (isBinary(N.Op)) {
+        const int A = operand(0), B = operand(1);
+        Out = NG.nregs++;
+        const int Op = N.Op == "Add" ? kEltAdd : N.Op == "Sub" ? kEltSub : N.Op == "Mul" ? kEltMul : kEltDiv;
+        NG.code.push_back(EltInstr{(uint8_t)Op, (uint8_t)Out, (uint8_t)A, (uint8_t)B});
+    } else { // BatchNormalization on a runtime tensor: y = x * s + t per channel
+        if (N.In.size() < 5) fail(N, "expected scale, bias, mean and variance");
+        const double Eps = N.attrF("epsilon", 1e-5);
+        std::vector<float> Sc((size_t)C), Sh((size_t)C);
+        for (size_t S = 1; S < 5; ++S)
+            if (host(N, S, "a BatchNormalization statistic").count() != (size_t)C) fail(N, "statistic length does not match the channels");
+        for (int Ch = 0; Ch < C; ++Ch) {
+            const double Gm = get(N, 1).at((size_t)Ch), Bt = get(N, 2).at((size_t)Ch);
+            const double Mn = get(N, 3).at((size_t)Ch), Vr = get(N, 4).at((size_t)Ch);
+            const double S = Gm / std::sqrt(Vr + Eps);
+            Sc[(size_t)Ch] = (float)S;
+            Sh[(size_t)Ch] = (float)(Bt - Mn * S);
+        }
+        const int A = operand(0);
+        EltSrc S1, S2;
+        S1.mode = S2.mode = kSrcChannel;
+        S1.constOff = addConst(Sc);
+        S2.constOff = addConst(Sh);
+        if (NG.srcs.size() + 2 > (size_t)kMaxEltSrcs) fail(N, "too many inputs for one fused launch");
+        NG.srcs.push_back(S1);
+        NG.srcs.push_back(S2);
+        const int RS = NG.nregs++, RT = NG.nregs++, RM = NG.nregs++;
+        Out = NG.nregs++;
+        NG.code.push_back(EltInstr{kEltLoad, (uint8_t)RS, (uint8_t)(NG.srcs.size() - 2), 0});
+        NG.code.push_back(EltInstr{kEltLoad, (uint8_t)RT, (uint8_t)(NG.srcs.size() - 1), 0});
+        NG.code.push_back(EltInstr{kEltMul, (uint8_t)RM, (uint8_t)A, (uint8_t)RS});
+        NG.code.push_back(EltInstr{kEltAdd, (uint8_t)Out, (uint8_t)RM, (uint8_t)RT});
+    }
+    if (NG.nregs > kMaxEltRegs || NG.code.size() > (size_t)kMaxEltCode) fail(N, "elementwise chain too long for one launch");
+    NG.outReg = Out;
+    Groups.push_back(NG);
+    Val V = runtimeVal(N, D);
+    V.group = (int)Groups.size() - 1;
+    V.v.buf = kPending;
+    V.v.C = C;
+    V.v.spatial = Spatial;
+    V.v.stride = roundUp(std::max(C, 1), kChunk);
+    Vals[N.Out[0]] = V;
+}
+
+// ---- the plan ----------------------------------------------------------------------------------------------------
+void Planner::run() {
+    // tensor contract (trt.cc:144-227)
+    std::set<std::string> Ins;
+    for (const std::string& I : G.Inputs)
+        if (!G.Inits.count(I)) Ins.insert(I);
+    std::string OutList;
+    for (const std::string& O : G.Outputs) OutList += (OutList.empty() ? "" : ", ") + O;
+    Outputs.insert(G.Outputs.begin(), G.Outputs.end());
+    if (!Ins.count("input")) throw Error("tensor contract: the graph has no input named 'input'");
+    for (const char* O : {"policy", "value", "draw"})
+        if (!Outputs.count(O))
+            throw Error(std::string("tensor contract: graph output '") + O + "' is missing (the graph's outputs: " + OutList + ")");
+    for (const std::string& I : Ins)
+        if (I != "input") throw Error("tensor contract: unexpected graph input '" + I + "'");
+
+    // the swish rewrite: Mul(x, Sigmoid(x)) -> Swish(x) when the Sigmoid feeds only the Mul
+    Nodes = G.Nodes;
+    P.nodes = (int)Nodes.size();
+    Skip.assign(Nodes.size(), false);
+    {
+        std::map<std::string, int> Cnt;
+        std::map<std::string, size_t> Producer;
+        for (size_t K = 0; K < Nodes.size(); ++K) {
+            for (const std::string& I : Nodes[K].In) ++Cnt[I];
+            for (const std::string& O : Nodes[K].Out) Producer[O] = K;
+        }
+        for (Node& N : Nodes) {
+            if (N.Op != "Mul" || N.In.size() != 2) continue;
+            for (int Side = 0; Side < 2; ++Side) {
+                const std::string& S = N.In[(size_t)Side];
+                const std::string& X = N.In[(size_t)(1 - Side)];
+                auto It = Producer.find(S);
+                if (It == Producer.end()) continue;
+                const Node& Sg = Nodes[It->second];
+                if (Sg.Op != "Sigmoid" || Sg.In.size() != 1 || Sg.In[0] != X || Cnt[S] != 1 || Outputs.count(S)) continue;
+                Skip[It->second] = true;
+                N.Op = "Swish";
+                N.In = {X};
+                break;
+            }
+        }
+    }
+    for (size_t K = 0; K < Nodes.size(); ++K) {
+        if (Skip[K]) continue;
+        const Node& N = Nodes[K];
+        if (!opSet().count(N.Op) && N.Op != "Swish") fail(N, "op '" + N.Op + "' is outside the supported op set (DESIGN.md section 13)");
+        for (const std::string& I : N.In)
+            if (!I.empty()) ++Uses[I];
+    }
+    for (const std::string& O : G.Outputs) ++Uses[O];
+
+    // constants
+    for (const auto& KV : G.Inits) {
+        Val V;
+        V.dims = KV.second.Dims;
+        V.isInt = !KV.second.IsFloat;
+        if (V.isInt) V.i = KV.second.I;
+        else {
+            V.f.assign(KV.second.F.begin(), KV.second.F.end());
+            P.params += KV.second.F.size();
+        }
+        Vals[KV.first] = V;
+    }
+    {   // the graph input: [N, numChannels, 9, 9] as the plane expansion writes it
+        for (size_t K = 0; K < G.Inputs.size(); ++K) {
+            if (G.Inputs[K] != "input") continue;
+            std::vector<int64_t> Decl;
+            if (K < G.InputInfos.size() && valueInfoDims(G.InputInfos[K], &Decl)) {
+                std::string First;
+                for (const Node& N : Nodes)
+                    for (const std::string& I : N.In)
+                        if (I == "input" && First.empty()) First = N.Name;
+                if (Decl.size() != 4 || (Decl[2] != 9 && Decl[2] != -1) || (Decl[3] != 9 && Decl[3] != -1))
+                    throw Error("graph input 'input' (read by node '" + First + "') is declared " + dimsStr(Decl) + ", not [N,C,9,9]");
+                if (Decl[1] > 0 && Decl[1] != NumChannels)
+                    throw Error("graph input 'input' (read by node '" + First + "') has " + std::to_string(Decl[1]) +
+                                " planes, the evaluator has " + std::to_string(NumChannels));
+            }
+        }
+        Val In;
+        In.runtime = true;
+        In.dims = {kBatch, NumChannels, 9, 9};
+        In.v.buf = -1;
+        In.v.C = NumChannels;
+        In.v.stride = roundUp(NumChannels, kChunk);
+        In.v.spatial = true;
+        In.producer = "input";
+        Vals["input"] = In;
+        P.planeStride = In.v.stride;
+    }
+
+    for (size_t K = 0; K < Nodes.size(); ++K) {
+        if (Skip[K]) continue;
+        const Node& N = Nodes[K];
+        const std::string& Op = N.Op;
+        if (N.Out.empty()) fail(N, "no output");
+        if (Op == "Constant") {
+            if (!Vals.count(N.Out[0])) fail(N, "unsupported Constant attribute (value tensor or value_float only)");
+            continue;
+        }
+        bool AnyRuntime = false;
+        for (const std::string& I : N.In)
+            if (!I.empty()) {
+                auto It = Vals.find(I);
+                if (It == Vals.end()) fail(N, "input '" + I + "' is not defined before its use");
+                AnyRuntime = AnyRuntime || It->second.runtime;
+            }
+        if (Op == "Shape" || !AnyRuntime) {
+            hostFold(N);
+            continue;
+        }
+        const Val& X = get(N, 0);
+        if (Op == "Conv" || Op == "Gemm" || Op == "MatMul") {
+            linear(N, K);
+        } else if (isAct(Op) || isBinary(Op) || Op == "BatchNormalization") {
+            if (Op == "BatchNormalization" && !X.runtime) fail(N, "expected a runtime input");
+            if (isBinary(Op) && !get(N, 0).runtime && !get(N, 1).runtime) fail(N, "constant operands only");
+            elementwise(N);
+        } else if (Op == "GlobalAveragePool" || Op == "ReduceMean") {
+            if (X.flatOfSpatial || !isSpatialDims(X.dims)) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
+            bool Keep = true;
+            if (Op == "ReduceMean") {
+                std::vector<int64_t> Axes = has(N, 1) ? ints(N, 1, "axes") : N.attrInts("axes", {});
+                for (int64_t& A : Axes) if (A < 0) A += 4;
+                std::sort(Axes.begin(), Axes.end());
+                if (Axes != std::vector<int64_t>{2, 3}) fail(N, "ReduceMean over axes {2,3} only");
+                Keep = N.attrI("keepdims", 1) != 0;
+            }
+            const int C = (int)X.dims[1];
+            Launch L;
+            L.kind = kLaunchMean;
+            L.name = N.Name;
+            L.in = ready(N.In[0]).v;
+            L.out = freshView(C, false);
+            Val V = runtimeVal(N, Keep ? std::vector<int64_t>{kBatch, C, 1, 1} : std::vector<int64_t>{kBatch, C});
+            V.v = L.out;
+            emit(L);
+            Vals[N.Out[0]] = V;
+        } else if (Op == "Flatten" || Op == "Reshape" || Op == "Squeeze" || Op == "Unsqueeze" || Op == "Identity") {
+            // an open elementwise group read only here stays open: the reshaped tensor is its new result
+            // (a [N,C,9,9] group that becomes [N,C*81] is emitted first: the flattened view reads its buffer)
+            bool MoveGroup = Vals.at(N.In[0]).group >= 0 && absorbable(N.In[0]);
+            Val Src = MoveGroup ? Vals.at(N.In[0]) : ready(N.In[0]);
+            const std::vector<int64_t> SD = Src.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)Src.v.C * 81} : Src.dims;
+            int64_t Rest = 1;
+            for (size_t J = 1; J < SD.size(); ++J) Rest *= SD[J];
+            std::vector<int64_t> ND;
+            if (Op == "Identity") ND = SD;
+            else if (Op == "Flatten") {
+                if (N.attrI("axis", 1) != 1) fail(N, "Flatten with axis 1 only");
+                ND = {kBatch, Rest};
+            } else if (Op == "Reshape") {
+                const std::vector<int64_t> Sh = ints(N, 1, "the target shape");
+                int64_t Known = 1;
+                int Infer = -1;
+                ND.assign(Sh.size(), 0);
+                for (size_t J = 0; J < Sh.size(); ++J) {
+                    int64_t V = Sh[J];
+                    if (V == 0 && J < SD.size()) V = SD[J];
+                    if (V == -1) { Infer = (int)J; continue; }
+                    ND[J] = V;
+                    if (V != kBatch) Known *= V;
+                }
+                bool HasBatch = std::count(ND.begin(), ND.end(), kBatch) == 1;
+                if (Infer >= 0) {
+                    if (HasBatch) {
+                        if (Known <= 0 || Rest % Known) fail(N, "cannot infer the -1 dimension");
+                        ND[(size_t)Infer] = Rest / Known;
+                    } else {
+                        if (Known != Rest) fail(N, "reshape would mix boards");
+                        ND[(size_t)Infer] = kBatch;
+                    }
+                }
+                if (ND.empty() || ND[0] != kBatch) fail(N, "the target shape " + dimsStr(ND) + " does not keep the batch first");
+            } else {
+                std::vector<int64_t> Axes = has(N, 1) ? ints(N, 1, "axes") : N.attrInts("axes", {});
+                ND = SD;
+                if (Op == "Unsqueeze") {
+                    const int64_t Rank = (int64_t)(SD.size() + Axes.size());
+                    for (int64_t& A : Axes) if (A < 0) A += Rank;
+                    std::sort(Axes.begin(), Axes.end());
+                    for (int64_t A : Axes) {
+                        if (A <= 0 || A > (int64_t)ND.size()) fail(N, "cannot unsqueeze the batch axis");
+                        ND.insert(ND.begin() + A, 1);
+                    }
+                } else {
+                    std::vector<int64_t> Keep;
+                    for (size_t J = 0; J < SD.size(); ++J) {
+                        bool Drop = Axes.empty() ? (J > 0 && SD[J] == 1) : false;
+                        for (int64_t A : Axes) Drop = Drop || (A < 0 ? A + (int64_t)SD.size() : A) == (int64_t)J;
+                        if (Drop && (J == 0 || SD[J] != 1)) fail(N, "squeezes a dimension that is not 1");
+                        if (!Drop) Keep.push_back(SD[J]);
+                    }
+                    ND = Keep;
+                }
+            }
+            int64_t NR = 1;
+            for (size_t J = 1; J < ND.size(); ++J) NR *= ND[J];
+            if (NR != Rest) fail(N, "element count changes: " + dimsStr(SD) + " -> " + dimsStr(ND));
+            const bool SrcSpatial = Src.flatOfSpatial || isSpatialDims(Src.dims);
+            const int64_t SrcC = Src.flatOfSpatial ? (int64_t)Src.v.C : SrcSpatial ? Src.dims[1] : -1;
+            if (MoveGroup && SrcSpatial && !isSpatialDims(ND)) {
+                MoveGroup = false;
+                Src = ready(N.In[0]);
+            }
+            Val V = Src;
+            V.producer = N.Name;
+            V.dims = ND;
+            if (SrcSpatial) {
+                if (isSpatialDims(ND) && ND[1] == SrcC) V.flatOfSpatial = false;
+                else if (ND.size() == 2) V.flatOfSpatial = true;
+                else fail(N, "a [N,C,9,9] tensor can become [N,C*81] or stay [N,C,9,9], not " + dimsStr(ND));
+            } else if (flatC(ND) < 0) {
+                fail(N, "a flat tensor cannot become " + dimsStr(ND));
+            }
+            if (!V.flatOfSpatial && !isSpatialDims(V.dims)) V.dims = ND;
+            if (MoveGroup) Groups[(size_t)V.group].out = N.Out[0];
+            Vals[N.Out[0]] = V;
+        } else if (Op == "Concat") {
+            int64_t Ax = N.attrI("axis", 1);
+            const size_t Rank = X.flatOfSpatial ? 2 : X.dims.size();
+            if (Ax < 0) Ax += (int64_t)Rank;
+            if (Ax != 1) fail(N, "Concat of runtime tensors along axis 1 only");
+            if (N.In.size() > (size_t)kMaxCopySegs) fail(N, "more than " + std::to_string(kMaxCopySegs) + " inputs");
+            Launch L;
+            L.kind = kLaunchConcat;
+            L.name = N.Name;
+            int Total = 0;
+            bool Sp = false;
+            std::vector<int64_t> D0;
+            for (size_t J = 0; J < N.In.size(); ++J) {
+                const Val& V = get(N, J);
+                if (!V.runtime) fail(N, "Concat of a runtime tensor and a constant");
+                const bool VS = !V.flatOfSpatial && isSpatialDims(V.dims);
+                if (J == 0) Sp = VS;
+                if (VS != Sp) fail(N, "Concat of [N,C,9,9] and flat tensors");
+                if (!Sp && (V.flatOfSpatial ? 2 : V.dims.size()) != Rank) fail(N, "Concat of different ranks");
+                CopySeg S;
+                S.v = V.flatOfSpatial ? plain(N.In[J], N.Name + " (flatten)") : ready(N.In[J]).v;
+                S.dstOff = Total;
+                Total += S.v.C;
+                L.segs.push_back(S);
+            }
+            L.out = freshView(Total, Sp);
+            std::vector<int64_t> ND = Sp ? std::vector<int64_t>{kBatch, Total, 9, 9} : std::vector<int64_t>{kBatch, Total};
+            if (!Sp) for (size_t J = 2; J < Rank; ++J) ND.push_back(1);
+            Val V = runtimeVal(N, ND);
+            V.v = L.out;
+            emit(L);
+            Vals[N.Out[0]] = V;
+        } else if (Op == "Slice") {
+            const Val Src = X.flatOfSpatial ? (plain(N.In[0], N.Name + " (flatten)"), Vals.at(N.In[0])) : ready(N.In[0]);
+            const std::vector<int64_t> St = ints(N, 1, "starts"), En = ints(N, 2, "ends");
+            std::vector<int64_t> Axes = has(N, 3) ? ints(N, 3, "axes") : std::vector<int64_t>();
+            const std::vector<int64_t> Sp = has(N, 4) ? ints(N, 4, "steps") : std::vector<int64_t>(St.size(), 1);
+            if (Axes.empty()) for (size_t J = 0; J < St.size(); ++J) Axes.push_back((int64_t)J);
+            if (St.size() != En.size() || Axes.size() != St.size() || Sp.size() != St.size()) fail(N, "malformed Slice");
+            Val V = Src;
+            V.producer = N.Name;
+            for (size_t J = 0; J < Axes.size(); ++J) {
+                int64_t A = Axes[J] < 0 ? Axes[J] + (int64_t)Src.dims.size() : Axes[J];
+                if (Sp[J] != 1) fail(N, "Slice with a step other than 1");
+                if (A == 1) {
+                    const int64_t Len = Src.v.C;
+                    int64_t S = St[J] < 0 ? St[J] + Len : St[J], E = En[J] < 0 ? En[J] + Len : En[J];
+                    S = std::max<int64_t>(0, std::min(S, Len));
+                    E = std::max<int64_t>(S, std::min(E, Len));
+                    if (E == S) fail(N, "empty slice");
+                    V.v.offset += (int)S;
+                    V.v.C = (int)(E - S);
+                    V.dims[1] = E - S;
+                } else {
+                    const int64_t Dim = A < (int64_t)Src.dims.size() ? Src.dims[(size_t)A] : 1;
+                    if (St[J] != 0 || (Dim != kBatch && En[J] < Dim)) fail(N, "Slice along an axis other than 1");
+                }
+            }
+            Vals[N.Out[0]] = V;
+        } else if (Op == "Gather" || Op == "Cast") {
+            fail(N, "applied to a runtime tensor (folded on shape values only)");
+        } else {
+            fail(N, "op '" + Op + "' is not supported on runtime tensors");
+        }
+    }
+    checkOutputs();
+    assignBuffers();
+}
+
+void Planner::checkOutputs() {
+    auto producerNode = [&](const std::string& T) -> const Node* {
+        for (const Node& N : Nodes)
+            for (const std::string& O : N.Out)
+                if (O == T) return &N;
+        return nullptr;
+    };
+    auto outFail = [&](const std::string& T, const std::string& Why) {
+        const Node* N = producerNode(T);
+        if (N) fail(*N, "output '" + T + "' " + Why);
+        throw Error("output '" + T + "' " + Why);
+    };
+    for (const char* O : {"policy", "value", "draw"}) {
+        auto It = Vals.find(O);
+        if (It == Vals.end()) outFail(O, "is never computed");
+        if (!It->second.runtime) outFail(O, "is a constant");
+        ready(O);
+    }
+    {
+        const Val& V = Vals.at("policy");
+        if (V.flatOfSpatial || isSpatialDims(V.dims)) {
+            if (V.v.C * 81 != 2187) outFail("policy", "has " + std::to_string(V.v.C * 81) + " values per position (expected: 2187)");
+            P.policy = V.v;
+        } else {
+            const int C = flatC(V.dims);
+            if (C != 2187) outFail("policy", "has " + std::to_string(C) + " values per position (expected: 2187)");
+            P.policy = V.v;
+        }
+    }
+    for (const char* O : {"value", "draw"}) {
+        const Val& V = Vals.at(O);
+        if (V.flatOfSpatial || isSpatialDims(V.dims) || flatC(V.dims) != 1)
+            outFail(O, "must hold one value per position, it is " + dimsStr(V.dims));
+        (O[0] == 'v' ? P.value : P.draw) = V.v;
+    }
+}
+
+// lifetimes -> physical buffers (a launch's output never shares a buffer with its inputs)
+void Planner::assignBuffers() {
+    const size_t NV = VirtStride.size();
+    std::vector<int> Last(NV, -1);
+    auto use = [&](const View& V, int I) {
+        if (V.buf >= 0) Last[(size_t)V.buf] = std::max(Last[(size_t)V.buf], I);
+    };
+    const int NL = (int)P.launches.size();
+    for (int I = 0; I < NL; ++I) {
+        const Launch& L = P.launches[(size_t)I];
+        use(L.in, I);
+        use(L.res, I);
+        for (const EltSrc& S : L.srcs) if (S.mode == kSrcSame || S.mode == kSrcBoard) use(S.v, I);
+        for (const CopySeg& S : L.segs) use(S.v, I);
+        use(L.out, I);
+    }
+    use(P.policy, NL);
+    use(P.value, NL);
+    use(P.draw, NL);
+    std::vector<int> Phys(NV, -1);
+    std::vector<bool> Free;
+    auto take = [&](int V) {
+        int Best = -1;
+        for (size_t K = 0; K < Free.size(); ++K)
+            if (Free[K]) {
+                const int S = VirtSpatial[(size_t)V] ? P.bufSpatialStride[K] : P.bufFlatStride[K];
+                if (Best < 0 || S >= VirtStride[(size_t)V]) { Best = (int)K; if (S >= VirtStride[(size_t)V]) break; }
+            }
+        if (Best < 0) {
+            Best = (int)Free.size();
+            Free.push_back(false);
+            P.bufSpatialStride.push_back(0);
+            P.bufFlatStride.push_back(0);
+        }
+        Free[(size_t)Best] = false;
+        int& S = VirtSpatial[(size_t)V] ? P.bufSpatialStride[(size_t)Best] : P.bufFlatStride[(size_t)Best];
+        S = std::max(S, VirtStride[(size_t)V]);
+        Phys[(size_t)V] = Best;
+    };
+    for (int I = 0; I < NL; ++I) {
+        const Launch& L = P.launches[(size_t)I];
+        take(L.out.buf);
+        for (size_t V = 0; V < NV; ++V)
+            if (Last[V] == I && Phys[V] >= 0) Free[(size_t)Phys[V]] = true;
+    }
+    auto map = [&](View& V) {
+        if (V.buf == kPending) throw Error("internal planner error: a launch reads an elementwise result before it is computed");
+        if (V.buf >= 0) V.buf = Phys[(size_t)V.buf];
+    };
+    for (Launch& L : P.launches) {
+        map(L.in);
+        map(L.res);
+        map(L.out);
+        for (EltSrc& S : L.srcs) if (S.mode == kSrcSame || S.mode == kSrcBoard) map(S.v);
+        for (CopySeg& S : L.segs) map(S.v);
+    }
+    map(P.policy);
+    map(P.value);
+    map(P.draw);
+    size_t Bytes = (size_t)P.planeStride * 81 * 4;
+    for (size_t K = 0; K < P.bufSpatialStride.size(); ++K)
+        Bytes += 4 * std::max((size_t)P.bufSpatialStride[K] * 81, (size_t)P.bufFlatStride[K]);
+    P.activationBytesPerPosition = Bytes;
+}
+
+} // namespace
+
+bool buildPlan(const void* Data, size_t Size, int NumChannels, GraphPlan* Plan, std::string* Err) {
+    try {
+        const Graph G = readModel(Span{(const unsigned char*)Data, Size});
+        GraphPlan P;
+        P.numChannels = NumChannels;
+        Planner(G, NumChannels, &P).run();
+        *Plan = std::move(P);
+        return true;
+    } catch (const std::exception& E) {
+        if (Err) *Err = E.what();
+        return false;
+    }
+}
+
+int countNodes(const void* Data, size_t Size) {
+    try {
+        return (int)readModel(Span{(const unsigned char*)Data, Size}).Nodes.size();
+    } catch (const std::exception&) {
+        return 0;
+    }
+}
+
+} // namespace graph
+} // namespace nsg

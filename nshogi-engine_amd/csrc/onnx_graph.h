@@ -1,0 +1,116 @@
+// onnx_graph.h -- the general graph path's host half: reads an ONNX model built from the closed op set of
+// DESIGN.md section 13, folds shape chains and BatchNorm, fuses epilogues and elementwise chains, assigns
+// activation buffers, and returns an immutable GraphPlan of launch records.  Host-only C++: no device code.
+//
+// Layout of every runtime tensor (the library's board-major, channel-innermost layout):
+//   spatial [N,C,9,9]           -> [row = board * 81 + square][stride] floats
+//   flat [N,C] / [N,C,1,1] / [N] -> [row = board][stride] floats
+// stride = C rounded up to 16 (the conv kernel's K chunk); channels C..stride-1 are written as zero by every kernel.
+// A view names a buffer plus a channel offset, so `Slice` along the channel axis costs no launch.
+#ifndef NSG_ONNX_GRAPH_H
+#define NSG_ONNX_GRAPH_H
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace nsg {
+namespace graph {
+
+constexpr int kChunk = 16;      // channel granule of every activation stride and of the conv kernel's K chunk
+constexpr int kCoutTile = 64;   // output channels per conv workgroup
+constexpr int kMaxEltSrcs = 8;  // inputs of one fused elementwise launch
+constexpr int kMaxEltCode = 32; // instructions of one fused elementwise launch
+constexpr int kMaxEltRegs = 16;
+constexpr int kMaxCopySegs = 8; // sources of one channel concat
+
+enum Act { kActNone = 0, kActRelu, kActSigmoid, kActTanh, kActSwish, kActSoftplus };
+
+// A runtime tensor as a launch sees it.  buf: -1 = the plane buffer (graph input), >= 0 = activation buffer.
+struct View {
+    int buf = -1;
+    int stride = 0;  // floats per row
+    int offset = 0;  // first channel inside the row
+    int C = 0;       // channels (a flat tensor: its width)
+    bool spatial = false;
+};
+
+// Elementwise program: registers r0..r15; opcodes below.  LOAD reads source `a` into register `dst`.
+enum EltOp { kEltLoad = 0, kEltAct, kEltAdd, kEltSub, kEltMul, kEltDiv };
+struct EltInstr {
+    uint8_t op, dst, a, b; // kEltAct: a = source register, b = Act; binary: dst = a (op) b
+};
+// How a source is read, relative to the element (row, c) of the output
+enum EltMode {
+    kSrcSame = 0,   // the view's (row, c): same kind as the output
+    kSrcBoard,      // flat view broadcast over squares: (row / 81, c)
+    kSrcChannel,    // constant per channel: weights[constOff + c]
+    kSrcScalar,     // constant: `scalar`
+};
+struct EltSrc {
+    int mode = kSrcScalar;
+    View v;
+    size_t constOff = 0;
+    float scalar = 0.f;
+};
+
+enum LaunchKind { kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten };
+struct CopySeg { View v; int dstOff = 0; };
+
+struct Launch {
+    int kind = kLaunchConv;
+    std::string name; // the ONNX node(s) it runs
+    View out;
+    // kLaunchConv: an implicit-GEMM conv (taps 9 or 1) or a dense layer (taps 1, rows = boards)
+    View in, res;    // res.buf == -2: no residual
+    bool dense = false;
+    int taps = 9;
+    int cinPad = 0;  // K = taps x cinPad
+    int coutTiles = 0;
+    size_t wOff = 0;    // packed weights [coutTiles][cinPad / 16][taps][16][64]
+    size_t biasOff = 0; // [coutTiles * 64]
+    int act = kActNone;
+    // kLaunchElt
+    std::vector<EltSrc> srcs;
+    std::vector<EltInstr> code;
+    int eltOut = 0;  // the register stored
+    // kLaunchMean / kLaunchFlatten: `in`; kLaunchConcat: segments
+    std::vector<CopySeg> segs;
+};
+
+struct GraphPlan {
+    int numChannels = 0;
+    int planeStride = 0;           // the plane buffer's stride (numChannels rounded up to 16)
+    std::vector<float> weights;    // every constant a launch reads, uploaded once per device
+    // activation buffers: the widest spatial and flat strides each one holds (bytes for B boards: bufferFloats)
+    std::vector<int> bufSpatialStride, bufFlatStride;
+    std::vector<Launch> launches;  // in order; the plane expansion before and the output scatter after are implicit
+    View policy, value, draw;      // policy: spatial C = 27 (read as c * 81 + square) or flat C = 2187
+    // reported by nsg_get_graph_info / nsg_inspect_onnx
+    int nodes = 0;
+    int convLaunches = 0;
+    uint64_t params = 0;
+    double flopsPerPosition = 0.0;
+    size_t activationBytesPerPosition = 0;
+};
+
+// Plans `data` (an ONNX ModelProto) for `numChannels` input planes.  Returns false and a message naming the node
+// on anything outside the op set or the tensor contract.
+bool buildPlan(const void* data, size_t size, int numChannels, GraphPlan* plan, std::string* error);
+
+// Nodes of an ONNX model's graph (0 when it cannot be read).
+int countNodes(const void* data, size_t size);
+
+// Floats activation buffer `i` needs for `batch` boards: a flat tensor is read by the conv kernel (a dense layer) in
+// groups of 81 rows, so its rows are padded to a multiple of 81.
+inline size_t bufferFloats(const GraphPlan& P, size_t i, int batch) {
+    const size_t s = (size_t)P.bufSpatialStride[i] * 81 * (size_t)batch;
+    const size_t f = (size_t)P.bufFlatStride[i] * (((size_t)batch + 80) / 81 * 81);
+    return s > f ? s : f;
+}
+
+} // namespace graph
+} // namespace nsg
+
+#endif

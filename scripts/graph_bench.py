@@ -1,0 +1,131 @@
+"""Throughput of the general graph path against the specialised path, on the same network.
+
+    python scripts/graph_bench.py [--out profiles/graph/graph_bench.json] [--batches 1,64,512]
+    python scripts/graph_bench.py --trace      # one shape for `rocprofv3 --kernel-trace --stats`
+    python scripts/graph_bench.py --summarize DIR/run_results.db   # per-kernel times and the conv's share of peak
+
+Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
+SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
+time with PyTorch's exporter.  evals/s = positions / wall time of `iters` computeBlocking calls after a warm-up.
+Also the SE net's load time (nsg_load on the .onnx file, planning and upload included).
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+
+
+def family_onnx(nsg, path):
+    w = nsg.weights.make_random(20, 256, seed=1, bn="random")
+    nsg.onnx_io.export_onnx(w, path)
+
+
+def se_onnx(path):
+    import torch
+    import make_onnx_graph_golden as mk
+    torch.manual_seed(5)
+    net = mk.randomize_bn(mk.SENet(C=86, F=256, blocks=20, VC=32, VH=256), 13).eval()
+    mk.export_model(net, path, 86, True)
+
+
+def rate(nsg, path, batch, prec="fp32", force=False, iters=50, warmup=5):
+    ev = nsg.Evaluator(0, batch, 86, precision=prec)
+    if force:
+        ev.set_graph_mode("force")
+    ev.load(path)
+    bb = nsg.synth.random_batch(batch, 86, seed=3)
+    for _ in range(warmup):
+        ev.compute_blocking(bb)
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        ev.compute_blocking(bb)
+    dt = time.perf_counter() - t0
+    info = ev.graph_info()
+    ev.close()
+    return batch * iters / dt, info
+
+
+TRACE_BATCH, TRACE_FORWARDS = 512, 23  # --trace: 3 warm-up + 20 timed forwards of the 20x256 net at B = 512
+F32_MFMA_PEAK = 157.3e12  # FLOP/s at the 2.4 GHz peak clock (MI355X_MICROARCH): the run's clock is not sampled
+
+
+def summarize(db):
+    """The kernel table of a --trace run (rocprofv3's SQLite output) and the 3x3 conv's share of the f32 MFMA peak:
+    algorithmic FLOPs (2 * 81 * 9 * Cin * Cout per board, real channel counts) over measured kernel time."""
+    import sqlite3
+    import statistics
+    c = sqlite3.connect(db)
+    print(f"{'kernel':60s} {'calls':>6s} {'total ms':>10s} {'avg us':>9s}")
+    for n, k, t, a in c.execute("select name, count(*), sum(end-start), avg(end-start) from kernels group by name "
+                                "order by sum(end-start) desc"):
+        short = n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        print(f"{short:60s} {k:6d} {t / 1e6:10.2f} {a / 1e3:9.1f}")
+    d = [r[0] for r in c.execute("select end-start from kernels where name like '%graphConv<9>%' order by start")]
+    per_fwd = 41  # the stem + 40 residual-block convs
+    fl_main = 2.0 * TRACE_BATCH * 81 * 9 * 256 * 256
+    fl_stem = 2.0 * TRACE_BATCH * 81 * 9 * 86 * 256
+    main_ns = [d[i] for i in range(len(d)) if i % per_fwd != 0]
+    m = statistics.median(main_ns) * 1e-9
+    print()
+    print(f"3x3 256->256 conv, B={TRACE_BATCH}: {fl_main / 1e9:.2f} GFLOP per launch, median {m * 1e6:.1f} us over "
+          f"{len(main_ns)} launches = {fl_main / m / 1e12:.1f} TFLOP/s = {fl_main / m / F32_MFMA_PEAK:.3f} of the f32 MFMA "
+          f"peak at the peak clock (the run's clock was not sampled)")
+    tot = sum(d) * 1e-9 / (len(d) / per_fwd)
+    print(f"all 3x3 launches of a forward: {tot * 1e3:.2f} ms for {(40 * fl_main + fl_stem) / 1e9:.1f} GFLOP = "
+          f"{(40 * fl_main + fl_stem) / tot / F32_MFMA_PEAK:.3f} of peak")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "graph", "graph_bench.json"))
+    ap.add_argument("--batches", default="1,64,512")
+    ap.add_argument("--trace", action="store_true", help="only the forced 20x256 general path at B=512, 20 forwards")
+    ap.add_argument("--summarize", metavar="DB", help="summarise the rocprofv3 database of a --trace run")
+    a = ap.parse_args()
+    if a.summarize:
+        summarize(a.summarize)
+        return
+    nsg = importlib.import_module("nshogi-engine_amd")
+    tmp = tempfile.mkdtemp()
+    fam = os.path.join(tmp, "family_20x256.onnx")
+    family_onnx(nsg, fam)
+    if a.trace:
+        r, info = rate(nsg, fam, TRACE_BATCH, force=True, iters=TRACE_FORWARDS - 3, warmup=3)
+        print(json.dumps({"trace_evals_per_s": r, "conv_flops_per_position": info["flops_per_position"]}))
+        return
+    se = os.path.join(tmp, "se_20x256.onnx")
+    se_onnx(se)
+    res = {"batches": [int(b) for b in a.batches.split(",")], "rows": {}}
+    for label, path, prec, force in (("family_20x256_general", fam, "fp32", True),
+                                     ("family_20x256_specialised_fp32", fam, "fp32", False),
+                                     ("family_20x256_specialised_f16m6", fam, "f16m6", False),
+                                     ("se_swish_20x256_general", se, "fp32", False)):
+        row = {}
+        for b in res["batches"]:
+            r, info = rate(nsg, path, b, prec, force, iters=20 if b >= 256 else 50)
+            row[str(b)] = round(r, 1)
+            row["path"] = info["path"]
+            row["launches"] = info["launches"]
+            row["flops_per_position"] = info["flops_per_position"]
+        res["rows"][label] = row
+        print(label, json.dumps(row), flush=True)
+    ev = nsg.Evaluator(0, 512, 86)
+    t0 = time.perf_counter()
+    ev.load(se)
+    res["se_load_seconds"] = round(time.perf_counter() - t0, 3)
+    ev.close()
+    print("se load seconds", res["se_load_seconds"])
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
