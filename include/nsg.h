@@ -104,7 +104,11 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    and value-hidden widths multiples of 64).  It runs at the evaluator's
  *    precision (nsg_set_precision);
  *  - otherwise the general graph path, when the model
- *    is built only from its closed op set.  A general graph always runs in
+ *    is built only from its closed op set (section 13.2): convolutional nets
+ *    with SE / global pooling, and transformer or conv-plus-attention nets
+ *    over the 81 squares as tokens [N,81,C] -- dense layers, LayerNorm, exact
+ *    GELU, a learned positional embedding and the multi-head attention
+ *    pattern of section 13.3, which runs as one launch per block.  A general graph always runs in
  *    exact fp32, whatever nsg_set_precision asked for.
  * When both refuse, the load fails with NSG_E_FORMAT and a message giving both
  * reasons, the general path's naming the node (the reference's parser
@@ -336,9 +340,9 @@ typedef struct nsg_graph_info {
     int launches;        /* general path: kernel launches per forward (plane expansion and output scatter
                             included); specialised path: 0 */
     int conv_launches;   /* general path: convolution and dense-layer launches per forward; specialised: 0 */
-    int reserved;
+    int attention_launches; /* general path: fused attention launches per forward (one per attention block) */
     uint64_t param_count;      /* float constants of the model */
-    double flops_per_position; /* general path: every conv and dense layer; specialised: as nsg_info's */
+    double flops_per_position; /* general path: every conv, dense layer and attention matmul; specialised: as nsg_info's */
     uint64_t activation_bytes_per_position; /* general path: device activation buffers per board; specialised: 0 */
     uint64_t activation_bytes; /* ... allocated for BatchSizeMax (0 from nsg_inspect_onnx) */
 } nsg_graph_info;

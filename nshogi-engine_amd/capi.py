@@ -61,7 +61,7 @@ class _Info(ctypes.Structure):
 class _GraphInfo(ctypes.Structure):
     _fields_ = [
         ("path", ctypes.c_int), ("precision", ctypes.c_int), ("nodes", ctypes.c_int),
-        ("launches", ctypes.c_int), ("conv_launches", ctypes.c_int), ("reserved", ctypes.c_int),
+        ("launches", ctypes.c_int), ("conv_launches", ctypes.c_int), ("attention_launches", ctypes.c_int),
         ("param_count", ctypes.c_uint64), ("flops_per_position", ctypes.c_double),
         ("activation_bytes_per_position", ctypes.c_uint64), ("activation_bytes", ctypes.c_uint64),
     ]
@@ -71,7 +71,7 @@ _PATH_NAMES = {0: "specialised", 1: "graph"}
 
 
 def _graph_info_dict(s):
-    d = {k: getattr(s, k) for k, _ in _GraphInfo._fields_ if k != "reserved"}
+    d = {k: getattr(s, k) for k, _ in _GraphInfo._fields_}
     d["path"] = _PATH_NAMES.get(s.path, s.path)
     d["precision"] = {v: k for k, v in _PREC_NAMES.items() if k not in ("f32", "f16")}.get(s.precision, s.precision)
     return d
@@ -212,7 +212,7 @@ class Evaluator:
 
     def graph_info(self):
         """nsg_get_graph_info: the path the loaded network runs on ("specialised" | "graph"), its arithmetic, ONNX
-        nodes, launches and conv launches per forward, parameters, FLOPs per position, activation bytes."""
+        nodes, launches, conv launches and attention launches per forward, parameters, FLOPs per position, activation bytes."""
         s = _GraphInfo()
         _check(self._lib.nsg_get_graph_info(self._h, ctypes.byref(s)))
         return _graph_info_dict(s)

@@ -28,6 +28,8 @@ __device__ inline float applyAct(float v, int act) {
     case kActTanh: return tanhf(v);
     case kActSwish: return v / (1.f + expf(-v));
     case kActSoftplus: return v > 20.f ? v : log1pf(expf(v)); // torch's threshold
+    case kActErf: return erff(v);
+    case kActGelu: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); // exact GELU
     default: return v;
     }
 }

@@ -1,4 +1,5 @@
-// graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_ops.hip).
+// graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_ops.hip,
+// graph_attention.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -31,7 +32,7 @@ struct EltArgs {
     const float* src[kMaxEltSrcs];
     int stride[kMaxEltSrcs];
     int offset[kMaxEltSrcs];
-    int mode[kMaxEltSrcs];
+    int mode[kMaxEltSrcs];  // EltMode; kSrcChannel and kSrcSquareChannel read constants at src
     float scalar[kMaxEltSrcs];
     uint32_t code[kMaxEltCode]; // op | dst << 8 | a << 16 | b << 24
     int ncode;
@@ -59,6 +60,17 @@ struct ConcatArgs {
     long rows;
 };
 hipError_t launchGraphConcat(const ConcatArgs& a, hipStream_t stream);
+
+// LayerNorm over the channels of each row (token rows or boards): y = (x - mean) / sqrt(var + eps) * gamma + beta, the
+// biased variance, channels in.C..outStride-1 written as zero.  One wave per row.
+hipError_t launchGraphLayerNorm(DevView in, const float* gamma, const float* beta, float eps, float* out,
+                                int outStride, long rows, hipStream_t stream);
+
+// Attention over the 81 squares, one workgroup per (board, head): out[:, h*d .. h*d+d-1] = softmax(scale * q_h k_h^T +
+// bias[h]) v_h.  q, k, v: token views of heads * headDim channels at offsets that are multiples of 4; headDim a
+// multiple of 4, at most kMaxHeadDim; bias: [heads][81][81] or null.
+hipError_t launchGraphAttention(DevView q, DevView k, DevView v, const float* bias, float scale, float* out,
+                                int outStride, int heads, int headDim, int boards, hipStream_t stream);
 
 // [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)
 hipError_t launchGraphFlatten(DevView in, float* out, int outStride, int boards, hipStream_t stream);

@@ -17,6 +17,8 @@ __device__ inline float applyAct(float v, int act) {
     case kActTanh: return tanhf(v);
     case kActSwish: return v / (1.f + expf(-v));
     case kActSoftplus: return v > 20.f ? v : log1pf(expf(v));
+    case kActErf: return erff(v);
+    case kActGelu: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); // exact GELU
     default: return v;
     }
 }
@@ -45,6 +47,7 @@ __global__ __launch_bounds__(kThreads) void graphElt(EltArgs a) {
             case kSrcSame: v = p[(size_t)row * a.stride[x] + a.offset[x] + c]; break;
             case kSrcBoard: v = p[(size_t)(row / 81) * a.stride[x] + a.offset[x] + c]; break;
             case kSrcChannel: v = p[c]; break;
+            case kSrcSquareChannel: v = p[(size_t)(row % 81) * a.C + c]; break;
             default: v = a.scalar[x]; break;
             }
             break;

@@ -906,7 +906,7 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
                 const gr::EltSrc& S = L.srcs[i];
                 a.mode[i] = S.mode;
                 a.scalar[i] = S.scalar;
-                if (S.mode == gr::kSrcChannel) a.src[i] = wts + S.constOff;
+                if (S.mode == gr::kSrcChannel || S.mode == gr::kSrcSquareChannel) a.src[i] = wts + S.constOff;
                 else if (S.mode != gr::kSrcScalar) { a.src[i] = ptr(S.v); a.stride[i] = S.v.stride; a.offset[i] = S.v.offset; }
             }
             for (size_t i = 0; i < L.code.size(); ++i)
@@ -936,9 +936,18 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
             NSG_HIP(gr::launchGraphConcat(a, s));
             break;
         }
-        default: // kLaunchFlatten
+        case gr::kLaunchLayerNorm:
+            NSG_HIP(gr::launchGraphLayerNorm(dv(L.in), wts + L.wOff, wts + L.biasOff, L.eps, ptr(L.out), L.out.stride, rowsOf(L.out), s));
+            break;
+        case gr::kLaunchAttention:
+            NSG_HIP(gr::launchGraphAttention(dv(L.in), dv(L.attK), dv(L.attV), L.hasBias ? wts + L.biasOff : nullptr, L.scale,
+                                             ptr(L.out), L.out.stride, L.heads, L.headDim, B, s));
+            break;
+        case gr::kLaunchFlatten:
             NSG_HIP(gr::launchGraphFlatten(dv(L.in), ptr(L.out), L.out.stride, B, s));
             break;
+        default:
+            return fail(NSG_E_INVALID, "internal error: unknown launch kind %d in the graph plan", L.kind);
         }
     }
     NSG_HIP(gr::launchGraphOutputs(dv(P.policy), P.policy.spatial, dv(P.value), dv(P.draw), (float*)ev->policy.p,
@@ -2121,6 +2130,7 @@ static void graphInfoFromPlan(const nsg::graph::GraphPlan& P, nsg_graph_info* in
     info->nodes = P.nodes;
     info->launches = (int)P.launches.size() + 2; // + plane expansion + output scatter
     info->conv_launches = P.convLaunches;
+    info->attention_launches = P.attentionLaunches;
     info->param_count = P.params;
     info->flops_per_position = P.flopsPerPosition;
     info->activation_bytes_per_position = P.activationBytesPerPosition;

@@ -29,6 +29,22 @@ std::string dimsStr(const std::vector<int64_t>& D) {
     return S + "]";
 }
 
+// Logical shapes a runtime tensor may have besides [N,C,9,9] and flat.  kFormToken is a full citizen (dense layers,
+// elementwise ops, LayerNorm, the mean over squares); [N,C,81] exists only between a Reshape and a Transpose; the
+// 4-D forms exist only inside the attention pattern and become one kLaunchAttention.
+enum Form {
+    kFormPlain = 0,
+    kFormToken,   // [N,81,C]
+    kFormChan3,   // [N,C,81]
+    kFormTok4,    // [N,81,H,d]: q, k or v split into heads
+    kFormHeads,   // [N,H,81,d]
+    kFormHeadsT,  // [N,H,d,81]: k transposed
+    kFormScores,  // [N,H,81,81] before the Softmax
+    kFormProbs,   // [N,H,81,81] after it
+    kFormHeadOut, // [N,H,81,d]: probs x v
+    kFormTokOut4, // [N,81,H,d]
+};
+
 // A tensor of the graph: a host value (constant or folded shape), or a runtime tensor on the device.
 struct Val {
     bool runtime = false;
@@ -40,6 +56,12 @@ struct Val {
     // runtime
     View v;
     bool flatOfSpatial = false; // a flattened spatial tensor [N, C*81] (index c*81 + square); v is the spatial view
+    int form = kFormPlain;      // another logical shape over the spatial rows (Form); v is the spatial view
+    // the attention pattern's state (forms kFormTok4 and later), carried from the Reshape of q to the final Reshape
+    double scale = 1.0;         // scalar factors folded so far
+    View attQ, attK, attV;      // kFormScores and later: the q and k token views; kFormHeadOut and later: v's
+    std::vector<double> bias;   // kFormScores and later: [H][81][81], empty = none
+    std::string chain;          // names of the nodes absorbed so far
     int group = -1;             // open elementwise group that computes it (v not yet assigned)
     std::string producer;       // node name
     size_t count() const { return isInt ? i.size() : f.size(); }
@@ -71,6 +93,7 @@ class Planner {
     const int NumChannels;
     std::map<std::string, Val> Vals;
     std::map<std::string, int> Uses; // live consumers (+1 for a graph output)
+    std::map<std::string, int> ShapeUses; // ... of which Shape nodes
     std::set<std::string> Outputs;
     std::vector<bool> Skip;          // nodes absorbed into an earlier launch
     std::vector<Node> Nodes;         // after the swish rewrite
@@ -132,18 +155,23 @@ class Planner {
             if (D[K] != 1) return -1;
         return (int)D[1];
     }
-    Val runtimeVal(const Node& N, const std::vector<int64_t>& Dims) const {
+    static bool isTokenDims(const std::vector<int64_t>& D) {
+        return D.size() == 3 && D[0] == kBatch && D[1] == 81 && D[2] > 0;
+    }
+    Val runtimeVal(const Node& N, const std::vector<int64_t>& Dims, int Form = kFormPlain) const {
         Val V;
         V.runtime = true;
         V.dims = Dims;
         V.producer = N.Name;
-        if (!isSpatialDims(Dims) && flatC(Dims) < 0)
-            fail(N, "output shape " + dimsStr(Dims) + " is neither [N,C,9,9] nor flat [N,C] / [N,C,1,1]");
+        V.form = Form;
+        if (Form == kFormToken ? !isTokenDims(Dims) : (!isSpatialDims(Dims) && flatC(Dims) < 0))
+            fail(N, "output shape " + dimsStr(Dims) + " is neither [N,C,9,9], a token tensor [N,81,C] nor flat [N,C] / [N,C,1,1]");
         return V;
     }
 
     void emit(Launch L) {
         if (L.kind == kLaunchConv) ++P.convLaunches;
+        if (L.kind == kLaunchAttention) ++P.attentionLaunches;
         P.launches.push_back(std::move(L));
     }
     void emitGroup(int Gi) {
@@ -196,6 +224,21 @@ class Planner {
     void hostFold(const Node& N);
     void linear(const Node& N, size_t Index);
     void elementwise(const Node& N);
+    void layerNorm(const Node& N);
+    bool formView(const Node& N);   // Transpose, and Reshape / Flatten to or from the forms above
+    bool attentionOp(const Node& N); // MatMul / Mul / Div / Add / Softmax on the attention pattern's 4-D tensors
+    void rewriteGelu();
+    std::vector<int64_t> reshapeTarget(const Node& N, const std::vector<int64_t>& SD);
+    // the tensor feeds one node only: the attention pattern's interior tensors are never materialised
+    // (a Shape node reads no data: torch emits one on q for `q.size(-1) ** -0.5`)
+    void interior(const Node& N, size_t Idx) const {
+        const std::string& T = N.In[Idx];
+        auto U = Uses.find(T);
+        auto S = ShapeUses.find(T);
+        const int Data = (U == Uses.end() ? 0 : U->second) - (S == ShapeUses.end() ? 0 : S->second);
+        if (Outputs.count(T) || Data != 1)
+            fail(N, "'" + N.In[Idx] + "' is an interior tensor of the attention pattern (DESIGN.md section 13.3) and has more than one consumer");
+    }
     void checkOutputs();
     void assignBuffers();
     bool absorbable(const std::string& T) const {
@@ -214,7 +257,7 @@ class Planner {
 };
 
 bool isAct(const std::string& Op) {
-    return Op == "Relu" || Op == "Sigmoid" || Op == "Tanh" || Op == "Softplus" || Op == "Swish";
+    return Op == "Relu" || Op == "Sigmoid" || Op == "Tanh" || Op == "Softplus" || Op == "Swish" || Op == "Erf" || Op == "Gelu";
 }
 int actOf(const std::string& Op) {
     if (Op == "Relu") return kActRelu;
@@ -222,6 +265,8 @@ int actOf(const std::string& Op) {
     if (Op == "Tanh") return kActTanh;
     if (Op == "Softplus") return kActSoftplus;
     if (Op == "Swish") return kActSwish;
+    if (Op == "Erf") return kActErf;
+    if (Op == "Gelu") return kActGelu;
     return kActNone;
 }
 bool isBinary(const std::string& Op) { return Op == "Add" || Op == "Sub" || Op == "Mul" || Op == "Div"; }
@@ -230,9 +275,9 @@ const std::set<std::string>& opSet() {
     static const std::set<std::string> S = {
         "Conv", "BatchNormalization", "Relu", "Sigmoid", "Tanh", "Softplus", "Add", "Sub", "Mul", "Div",
         "GlobalAveragePool", "ReduceMean", "Flatten", "Reshape", "Squeeze", "Unsqueeze", "Gemm", "MatMul",
-        "Concat", "Slice", "Identity", "Constant",
+        "Concat", "Slice", "Identity", "Constant", "Transpose", "LayerNormalization", "Erf", "Softmax",
         // folded on the host only (shape chains): refused on a runtime tensor
-        "Shape", "Gather", "Cast"};
+        "Shape", "Gather", "Cast", "Pow", "Sqrt"};
     return S;
 }
 
@@ -424,6 +469,17 @@ void Planner::hostFold(const Node& N) {
         Out() = R;
         return;
     }
+    if (Op == "Sqrt" || Op == "Pow") { // torch emits them for `d ** -0.5` when d comes from size()
+        const Val* Y = Op == "Pow" ? &host(N, 1, "the exponent") : nullptr;
+        if (Y && Y->count() != 1 && Y->count() != X.count()) fail(N, "constant folding supports equal shapes or a scalar exponent");
+        R.dims = X.dims;
+        for (size_t K = 0; K < X.count(); ++K) {
+            if (X.isInt && X.i[K] == kBatch) fail(N, "arithmetic on the symbolic batch dimension");
+            R.f.push_back(Y ? std::pow(X.at(K), Y->at(Y->count() == 1 ? 0 : K)) : std::sqrt(X.at(K)));
+        }
+        Out() = R;
+        return;
+    }
     fail(N, "is applied to constants only; folding it is not supported");
 }
 
@@ -432,6 +488,8 @@ void Planner::linear(const Node& N, size_t Index) {
     const Val& X = get(N, 0);
     if (!X.runtime) fail(N, "the data input is a constant");
     const bool Dense = N.Op != "Conv";
+    const bool Tok = X.form == kFormToken; // a Linear over tokens: the 1x1 form of the conv, rows = (board, square)
+    if (Tok && N.Op != "MatMul") fail(N, "a token tensor " + dimsStr(X.dims) + " feeds MatMul, not " + N.Op);
     int Cin = 0, Cout = 0, K = 1;
     std::vector<double> W, Bias; // W[cout][cin][taps]
     std::string Name = N.Name;
@@ -472,8 +530,8 @@ void Planner::linear(const Node& N, size_t Index) {
         }
         Cout = (int)(TransB ? Wt.dims[0] : Wt.dims[1]);
         Cin = (int)(TransB ? Wt.dims[1] : Wt.dims[0]);
-        const int XC = X.flatOfSpatial ? X.v.C * 81 : flatC(X.dims);
-        if (X.dims.size() != 2 && !X.flatOfSpatial) fail(N, "input " + dimsStr(X.dims) + " is not 2-D [N,K]");
+        const int XC = Tok ? (int)X.dims[2] : X.flatOfSpatial ? X.v.C * 81 : flatC(X.dims);
+        if (X.dims.size() != 2 && !X.flatOfSpatial && !Tok) fail(N, "input " + dimsStr(X.dims) + " is not 2-D [N,K]");
         if (XC != Cin) fail(N, "the weight expects K = " + std::to_string(Cin) + ", '" + N.In[0] + "' has " + std::to_string(XC));
         W.assign((size_t)Cout * Cin, 0.0);
         for (int O = 0; O < Cout; ++O)
@@ -487,7 +545,10 @@ void Planner::linear(const Node& N, size_t Index) {
         }
     }
     const int Taps = K * K;
-    std::vector<int64_t> Dims = Dense ? std::vector<int64_t>{kBatch, Cout} : std::vector<int64_t>{kBatch, Cout, 9, 9};
+    std::vector<int64_t> Dims = Tok ? std::vector<int64_t>{kBatch, 81, Cout}
+                                    : Dense ? std::vector<int64_t>{kBatch, Cout} : std::vector<int64_t>{kBatch, Cout, 9, 9};
+    const int ChanAxis = Tok ? 2 : 1;
+    const int OutForm = Tok ? kFormToken : kFormPlain;
     // epilogue: [BatchNorm | constant per-channel Add]*  [+ runtime residual]  [activation]
     std::string Cur = N.Out[0];
     std::string Res;
@@ -518,10 +579,10 @@ void Planner::linear(const Node& N, size_t Index) {
                 std::vector<int64_t> BD;
                 if (!broadcast(Dims, O.dims, &BD) || BD != Dims) break;
                 const std::vector<int> Ax = variesAlong(O.dims, Dims.size());
-                if (!(Ax.empty() || (Ax.size() == 1 && Ax[0] == 1))) break;
+                if (!(Ax.empty() || (Ax.size() == 1 && Ax[0] == ChanAxis))) break;
                 for (int Ch = 0; Ch < Cout; ++Ch) Bias[(size_t)Ch] += O.at(Ax.empty() ? 0 : (size_t)Ch);
             } else {
-                if (!Res.empty() || Act != kActNone || O.flatOfSpatial || O.dims != Dims) break;
+                if (!Res.empty() || Act != kActNone || O.flatOfSpatial || O.dims != Dims || O.form != OutForm) break;
                 Res = Other;
             }
         } else if (isAct(C->Op) && Act == kActNone && C->In[0] == Cur) {
@@ -538,7 +599,7 @@ void Planner::linear(const Node& N, size_t Index) {
     Launch L;
     L.kind = kLaunchConv;
     L.name = Name;
-    L.dense = Dense;
+    L.dense = Dense && !Tok;
     L.taps = Taps;
     L.in = plain(N.In[0], N.Name + " (input copy)");
     L.cinPad = roundUp(Cin, kChunk);
@@ -564,9 +625,9 @@ void Planner::linear(const Node& N, size_t Index) {
         for (int O = 0; O < Cout; ++O) Bf[(size_t)O] = (float)Bias[(size_t)O];
         L.biasOff = addConst(Bf);
     }
-    L.out = freshView(Cout, !Dense);
-    P.flopsPerPosition += 2.0 * (Dense ? 1 : 81) * Taps * (double)Cin * Cout;
-    Val V = runtimeVal(N, Dims);
+    L.out = freshView(Cout, !L.dense);
+    P.flopsPerPosition += 2.0 * (L.dense ? 1 : 81) * Taps * (double)Cin * Cout;
+    Val V = runtimeVal(N, Dims, OutForm);
     V.v = L.out;
     V.producer = N.Name;
     emit(L);
@@ -587,11 +648,15 @@ void Planner::elementwise(const Node& N) {
         else D = Bd;
         InDims.push_back(Di);
     }
+    bool Tok = false; // a token operand makes the result a token tensor
+    for (size_t K = 0; K < Arity; ++K) Tok = Tok || (get(N, K).runtime && get(N, K).form == kFormToken);
+    if (Tok && !isTokenDims(D)) fail(N, "a token tensor broadcast to " + dimsStr(D));
     const bool Spatial = isSpatialDims(D);
-    const int C = Spatial ? (int)D[1] : flatC(D);
-    if (C < 0) fail(N, "output shape " + dimsStr(D) + " is neither [N,C,9,9] nor flat");
+    const int C = Tok ? (int)D[2] : Spatial ? (int)D[1] : flatC(D);
+    if (C < 0) fail(N, "output shape " + dimsStr(D) + " is neither [N,C,9,9], a token tensor nor flat");
+    const int ChanAxis = Tok ? 2 : 1;
     Group NG;
-    NG.spatial = Spatial;
+    NG.spatial = Spatial || Tok;
     NG.C = C;
     NG.name = N.Name;
     NG.out = N.Out[0];
@@ -606,13 +671,23 @@ void Planner::elementwise(const Node& N) {
                 if (V.count() < 1) fail(N, "empty constant");
                 S.mode = kSrcScalar;
                 S.scalar = (float)V.at(0);
-            } else if (Ax.size() == 1 && Ax[0] == 1 && D.size() >= 2) {
+            } else if (Ax.size() == 1 && Ax[0] == ChanAxis && D.size() >= 2) {
                 std::vector<float> F((size_t)C);
                 for (int Ch = 0; Ch < C; ++Ch) F[(size_t)Ch] = (float)V.at((size_t)Ch);
                 S.mode = kSrcChannel;
                 S.constOff = addConst(F);
+            } else if ((Tok && Ax == std::vector<int>{1, 2}) || (Spatial && Ax == std::vector<int>{1, 2, 3})) {
+                // a learned positional embedding, [81,C] on tokens or [C,9,9] on a spatial tensor: stored [square][C]
+                if (V.count() != (size_t)C * 81) fail(N, "constant of shape " + dimsStr(InDims[K]) + " does not cover " + dimsStr(D));
+                std::vector<float> F((size_t)C * 81);
+                for (int Sq = 0; Sq < 81; ++Sq)
+                    for (int Ch = 0; Ch < C; ++Ch)
+                        F[(size_t)Sq * C + Ch] = (float)V.at(Tok ? (size_t)Sq * C + Ch : (size_t)Ch * 81 + Sq);
+                S.mode = kSrcSquareChannel;
+                S.constOff = addConst(F);
             } else {
-                fail(N, "constant of shape " + dimsStr(InDims[K]) + " broadcast to " + dimsStr(D) + " (per-channel and scalar constants only)");
+                fail(N, "constant of shape " + dimsStr(InDims[K]) + " broadcast to " + dimsStr(D) +
+                            " (per-channel, per-(square, channel) and scalar constants only)");
             }
             if (NG.srcs.size() >= (size_t)kMaxEltSrcs) fail(N, "too many inputs for one fused launch");
             NG.srcs.push_back(S);
@@ -622,13 +697,13 @@ void Planner::elementwise(const Node& N) {
         }
         // runtime operand: how it varies relative to the output
         const std::vector<int64_t>& Di = InDims[K];
-        const bool Same = Di == D || (flatC(Di) == C && !Spatial && flatC(D) == C);
-        const bool Board = Spatial && !V.flatOfSpatial && flatC(Di) == C && Di.size() == 4;
+        const bool Same = Tok ? (V.form == kFormToken && Di == D) : (Di == D || (flatC(Di) == C && !Spatial && flatC(D) == C));
+        const bool Board = !Tok && Spatial && !V.flatOfSpatial && flatC(Di) == C && Di.size() == 4;
         if (!Same && !Board) fail(N, "operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
         // an open group used only here: inline its program
         const Group* Open = V.group >= 0 ? &Groups[(size_t)V.group] : nullptr;
         const bool Domain = Open && !V.flatOfSpatial && Open->C == C &&
-                            (Open->spatial == Spatial || (Board && !Open->spatial));
+                            (Open->spatial == NG.spatial || (Board && !Open->spatial));
         if (Domain && absorbable(Name)) {
             Group& Gr = Groups[(size_t)V.group];
             if (NG.srcs.size() + Gr.srcs.size() <= (size_t)kMaxEltSrcs && NG.code.size() + Gr.code.size() + 2 <= (size_t)kMaxEltCode &&
@@ -705,13 +780,372 @@ void Planner::elementwise(const Node& N) {
     if (NG.nregs > kMaxEltRegs || NG.code.size() > (size_t)kMaxEltCode) fail(N, "elementwise chain too long for one launch");
     NG.outReg = Out;
     Groups.push_back(NG);
-    Val V = runtimeVal(N, D);
+    Val V = runtimeVal(N, D, Tok ? kFormToken : kFormPlain);
     V.group = (int)Groups.size() - 1;
     V.v.buf = kPending;
     V.v.C = C;
-    V.v.spatial = Spatial;
+    V.v.spatial = NG.spatial;
     V.v.stride = roundUp(std::max(C, 1), kChunk);
     Vals[N.Out[0]] = V;
+}
+
+// ---- LayerNormalization over the channels of a token tensor or of a flat [N,C] tensor ------------------------------
+void Planner::layerNorm(const Node& N) {
+    const Val& X = get(N, 0);
+    const bool Tok = X.form == kFormToken;
+    if (!Tok && (X.flatOfSpatial || X.dims.size() != 2 || flatC(X.dims) < 0))
+        fail(N, "input " + dimsStr(X.dims) + " is neither a token tensor [N,81,C] nor flat [N,C]");
+    const int64_t Rank = (int64_t)X.dims.size();
+    int64_t Axis = N.attrI("axis", -1);
+    if (Axis < 0) Axis += Rank;
+    if (Axis != Rank - 1) fail(N, "LayerNormalization over the last axis (the channels) only");
+    const int C = (int)X.dims[(size_t)Rank - 1];
+    const Val& Sc = host(N, 1, "the scale");
+    if (Sc.count() != (size_t)C) fail(N, "scale length does not match the channels");
+    std::vector<float> Gm((size_t)C), Bt((size_t)C, 0.f);
+    for (int Ch = 0; Ch < C; ++Ch) Gm[(size_t)Ch] = (float)Sc.at((size_t)Ch);
+    if (has(N, 2)) {
+        const Val& B = host(N, 2, "the bias");
+        if (B.count() != (size_t)C) fail(N, "bias length does not match the channels");
+        for (int Ch = 0; Ch < C; ++Ch) Bt[(size_t)Ch] = (float)B.at((size_t)Ch);
+    }
+    if (N.Out.size() > 1 && !N.Out[1].empty() && Uses.count(N.Out[1])) fail(N, "the mean / inverse-deviation outputs are not supported");
+    Launch L;
+    L.kind = kLaunchLayerNorm;
+    L.name = N.Name;
+    L.in = ready(N.In[0]).v;
+    L.out = freshView(C, Tok);
+    L.wOff = addConst(Gm);
+    L.biasOff = addConst(Bt);
+    L.eps = (float)N.attrF("epsilon", 1e-5);
+    Val V = runtimeVal(N, X.dims, X.form);
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+}
+
+// The dims a Reshape of a tensor of dims SD produces (batch symbolic).
+std::vector<int64_t> Planner::reshapeTarget(const Node& N, const std::vector<int64_t>& SD) {
+    int64_t Rest = 1;
+    for (size_t J = 1; J < SD.size(); ++J) Rest *= SD[J];
+    std::vector<int64_t> ND;
+    const std::vector<int64_t> Sh = ints(N, 1, "the target shape");
+    int64_t Known = 1;
+    int Infer = -1;
+    ND.assign(Sh.size(), 0);
+    for (size_t J = 0; J < Sh.size(); ++J) {
+        int64_t V = Sh[J];
+        if (V == 0 && J < SD.size()) V = SD[J];
+        if (V == -1) { Infer = (int)J; continue; }
+        ND[J] = V;
+        if (V != kBatch) Known *= V;
+    }
+    const bool HasBatch = std::count(ND.begin(), ND.end(), kBatch) == 1;
+    if (Infer >= 0) {
+        if (HasBatch) {
+            if (Known <= 0 || Rest % Known) fail(N, "cannot infer the -1 dimension");
+            ND[(size_t)Infer] = Rest / Known;
+        } else {
+            if (Known != Rest) fail(N, "reshape would mix boards");
+            ND[(size_t)Infer] = kBatch;
+        }
+    }
+    if (ND.empty() || ND[0] != kBatch) fail(N, "the target shape " + dimsStr(ND) + " does not keep the batch first");
+    int64_t NR = 1;
+    for (size_t J = 1; J < ND.size(); ++J) NR *= ND[J];
+    if (NR != Rest) fail(N, "element count changes: " + dimsStr(SD) + " -> " + dimsStr(ND));
+    return ND;
+}
+
+// ---- views between [N,C,9,9], [N,C,81], tokens [N,81,C] and the attention pattern's 4-D shapes: no launch, except
+// the Reshape that closes the attention pattern.  Returns false when N is not such a view (the caller goes on).
+bool Planner::formView(const Node& N) {
+    const std::string& Op = N.Op;
+    if (Op != "Transpose" && Op != "Reshape" && Op != "Flatten" && Op != "Identity") return false;
+    const Val& X0 = get(N, 0);
+    if (!X0.runtime) return false;
+    if (Op == "Identity") {
+        if (X0.form == kFormPlain) return false;
+        if (X0.form >= kFormChan3) interior(N, 0);
+        Val V = ready(N.In[0]);
+        Vals[N.Out[0]] = V;
+        return true;
+    }
+    const std::vector<int64_t> Perm = N.attrInts("perm", {});
+    auto set = [&](Val V, int Form, std::vector<int64_t> Dims) {
+        V.form = Form;
+        V.dims = std::move(Dims);
+        V.producer = N.Name;
+        V.chain += (V.chain.empty() ? "" : "+") + N.Name;
+        Vals[N.Out[0]] = V;
+        return true;
+    };
+    if (Op == "Transpose") {
+        const int F = X0.form;
+        if (F == kFormPlain) return false; // refused by the caller, with the shapes
+        if (F >= kFormChan3) interior(N, 0);
+        const Val X = F == kFormToken ? ready(N.In[0]) : X0;
+        const std::vector<int64_t>& D = X.dims;
+        if ((F == kFormToken || F == kFormChan3) && Perm == std::vector<int64_t>{0, 2, 1}) {
+            Val V = X;
+            V.chain.clear();
+            return set(V, F == kFormToken ? kFormChan3 : kFormToken, {kBatch, D[2], D[1]});
+        }
+        if (F == kFormTok4 && Perm == std::vector<int64_t>{0, 2, 1, 3}) return set(X, kFormHeads, {kBatch, D[2], 81, D[3]});
+        if (F == kFormTok4 && Perm == std::vector<int64_t>{0, 2, 3, 1}) return set(X, kFormHeadsT, {kBatch, D[2], D[3], 81});
+        if (F == kFormHeads && Perm == std::vector<int64_t>{0, 1, 3, 2}) return set(X, kFormHeadsT, {kBatch, D[1], D[3], 81});
+        if (F == kFormHeadOut && Perm == std::vector<int64_t>{0, 2, 1, 3}) return set(X, kFormTokOut4, {kBatch, 81, D[1], D[3]});
+        fail(N, "Transpose of " + dimsStr(D) + " with perm " + dimsStr(Perm) + " is outside the token-view and attention patterns (DESIGN.md section 13.3)");
+    }
+    // Reshape / Flatten
+    const int F = X0.form;
+    const bool PlainSpatial = F == kFormPlain && !X0.flatOfSpatial && isSpatialDims(X0.dims);
+    if (F == kFormPlain && !PlainSpatial) return false;
+    if (PlainSpatial) {
+        // only Reshape to [N,C,81] is taken here (torch's flatten(2)); every other view is the existing code's.  ONNX's
+        // own Flatten with axis 2 gives [N*C,81], which mixes boards, and is refused there.
+        if (Op != "Reshape") return false;
+        const Val& ShV = get(N, 1);
+        if (ShV.runtime || ShV.count() != 3) return false;
+        const std::vector<int64_t> ND = reshapeTarget(N, X0.dims);
+        if (ND != std::vector<int64_t>{kBatch, X0.dims[1], 81}) return false;
+        Val V = ready(N.In[0]);
+        V.chain.clear();
+        return set(V, kFormChan3, ND);
+    }
+    if (Op == "Flatten" && !(F == kFormChan3 && N.attrI("axis", 1) == 1))
+        fail(N, "Flatten of " + dimsStr(X0.dims) + " is outside the token-view patterns");
+    if (F >= kFormChan3) interior(N, 0);
+    const std::vector<int64_t> ND = Op == "Flatten" ? std::vector<int64_t>{kBatch, X0.dims[1] * 81} : reshapeTarget(N, X0.dims);
+    if (F == kFormChan3) { // the way back: [N,C,81] -> [N,C,9,9] or the flattened [N,C*81]
+        Val V = X0;
+        V.form = kFormPlain;
+        V.producer = N.Name;
+        V.chain.clear();
+        if (isSpatialDims(ND) && ND[1] == X0.dims[1]) V.dims = ND;
+        else if (ND == std::vector<int64_t>{kBatch, X0.dims[1] * 81}) { V.dims = {kBatch, X0.dims[1], 9, 9}; V.flatOfSpatial = true; }
+        else fail(N, "a [N,C,81] tensor can become [N,C,9,9] or [N,C*81], not " + dimsStr(ND));
+        Vals[N.Out[0]] = V;
+        return true;
+    }
+    if (F == kFormToken) {
+        if (ND == X0.dims) { Val V = ready(N.In[0]); V.producer = N.Name; Vals[N.Out[0]] = V; return true; }
+        const int C = (int)X0.dims[2];
+        if (ND.size() != 4 || ND[1] != 81 || ND[2] <= 0 || ND[3] <= 0 || ND[2] * ND[3] != C)
+            fail(N, "a token tensor " + dimsStr(X0.dims) + " can be split into heads [N,81,H,d], not reshaped to " + dimsStr(ND));
+        const int64_t Hd = ND[3];
+        if (Hd % 4 != 0 || Hd > kMaxHeadDim)
+            fail(N, "head dimension " + std::to_string(Hd) + ": the attention kernel takes multiples of 4 up to " + std::to_string(kMaxHeadDim));
+        // q * scale (or k * scale) right before the split: an open group of one scalar Mul / Div is folded into the scale
+        Val V;
+        bool Peeled = false;
+        if (X0.group >= 0 && absorbable(N.In[0])) {
+            const Group& Gr = Groups[(size_t)X0.group];
+            if (Gr.open && Gr.srcs.size() == 2 && Gr.code.size() == 3 && Gr.code[0].op == kEltLoad && Gr.code[1].op == kEltLoad &&
+                (Gr.code[2].op == kEltMul || Gr.code[2].op == kEltDiv)) {
+                const int A = Gr.code[2].a, B = Gr.code[2].b; // registers loaded by code[0] and code[1]
+                const EltSrc& SA = Gr.srcs[Gr.code[A == Gr.code[0].dst ? 0 : 1].a];
+                const EltSrc& SB = Gr.srcs[Gr.code[B == Gr.code[0].dst ? 0 : 1].a];
+                const bool Mul = Gr.code[2].op == kEltMul;
+                const EltSrc* Rt = SA.mode == kSrcSame ? &SA : (Mul && SB.mode == kSrcSame) ? &SB : nullptr;
+                const EltSrc* Cs = Rt == &SA ? &SB : &SA;
+                if (A != B && Rt && Cs->mode == kSrcScalar && Gr.outReg == Gr.code[2].dst) {
+                    V = X0;
+                    V.group = -1;
+                    V.v = Rt->v;
+                    V.scale = Mul ? (double)Cs->scalar : 1.0 / (double)Cs->scalar;
+                    V.chain = Gr.name;
+                    Groups[(size_t)X0.group].open = false;
+                    Peeled = true;
+                }
+            }
+        }
+        if (!Peeled) {
+            V = ready(N.In[0]);
+            V.scale = 1.0;
+            V.chain.clear();
+        }
+        if (V.v.offset % 4 != 0) fail(N, "'" + N.In[0] + "' starts at channel " + std::to_string(V.v.offset) + " of its row: the attention kernel reads views at multiples of 4");
+        return set(V, kFormTok4, ND);
+    }
+    if (F == kFormTokOut4) { // the Reshape that closes the pattern: one launch
+        const int64_t H = X0.dims[2], Hd = X0.dims[3];
+        if (ND != std::vector<int64_t>{kBatch, 81, H * Hd})
+            fail(N, "the attention output " + dimsStr(X0.dims) + " is reshaped to " + dimsStr(ND) + ", not to [N,81,H*d]");
+        Launch L;
+        L.kind = kLaunchAttention;
+        L.name = X0.chain + "+" + N.Name;
+        L.in = X0.attQ;
+        L.attK = X0.attK;
+        L.attV = X0.attV;
+        L.heads = (int)H;
+        L.headDim = (int)Hd;
+        L.scale = (float)X0.scale;
+        L.hasBias = !X0.bias.empty();
+        if (L.hasBias) {
+            std::vector<float> Bf(X0.bias.begin(), X0.bias.end());
+            L.biasOff = addConst(Bf);
+        }
+        L.out = freshView((int)(H * Hd), true);
+        P.flopsPerPosition += 2.0 * (2.0 * 81 * 81 * (double)Hd) * (double)H; // q k^T and probs x v
+        Val V = runtimeVal(N, ND, kFormToken);
+        V.v = L.out;
+        emit(L);
+        Vals[N.Out[0]] = V;
+        return true;
+    }
+    fail(N, "Reshape of " + dimsStr(X0.dims) + " is outside the token-view and attention patterns (DESIGN.md section 13.3)");
+}
+
+// ---- the attention pattern's arithmetic: q k^T, the scalar factors, the constant bias, the Softmax, probs x v.
+// Nothing is launched here: the state travels in the Val until the closing Reshape (formView).
+bool Planner::attentionOp(const Node& N) {
+    const std::string& Op = N.Op;
+    const bool Binary = Op == "MatMul" || Op == "Mul" || Op == "Div" || Op == "Add";
+    if (!Binary && Op != "Softmax") return false;
+    const Val& A = get(N, 0);
+    const Val* B = Binary ? &get(N, 1) : nullptr;
+    const int FA = A.runtime ? A.form : kFormPlain, FB = B && B->runtime ? B->form : kFormPlain;
+    if (FA < kFormTok4 && FB < kFormTok4) return false;
+    auto put = [&](Val V, int Form, std::vector<int64_t> Dims) {
+        V.form = Form;
+        V.dims = std::move(Dims);
+        V.producer = N.Name;
+        V.chain += "+" + N.Name;
+        Vals[N.Out[0]] = V;
+        return true;
+    };
+    if (Op == "Softmax") {
+        if (FA != kFormScores) fail(N, "Softmax on " + dimsStr(A.dims) + ": only the softmax over the keys of [N,H,81,81] attention scores is supported");
+        int64_t Axis = N.attrI("axis", -1);
+        if (Axis < 0) Axis += 4;
+        if (Axis != 3) fail(N, "Softmax over axis " + std::to_string(N.attrI("axis", -1)) + " of the attention scores: the keys (axis -1) only");
+        interior(N, 0);
+        return put(A, kFormProbs, A.dims);
+    }
+    if (Op == "MatMul") {
+        if (FA == kFormHeads && FB == kFormHeadsT) {
+            interior(N, 0);
+            interior(N, 1);
+            if (A.dims[1] != B->dims[1] || A.dims[3] != B->dims[2])
+                fail(N, "q " + dimsStr(A.dims) + " and k^T " + dimsStr(B->dims) + " do not agree in heads and head dimension");
+            Val V = A;
+            V.attQ = A.v;
+            V.attK = B->v;
+            V.scale = A.scale * B->scale;
+            V.chain = A.chain + "+" + B->chain;
+            V.bias.clear();
+            return put(V, kFormScores, {kBatch, A.dims[1], 81, 81});
+        }
+        if (FA == kFormProbs && FB == kFormHeads) {
+            interior(N, 0);
+            interior(N, 1);
+            if (B->scale != 1.0) fail(N, "a scalar factor on v is not part of the attention pattern");
+            if (A.dims[1] != B->dims[1]) fail(N, "the attention weights have " + std::to_string(A.dims[1]) + " heads, v has " + std::to_string(B->dims[1]));
+            const int64_t QD = A.attQ.C / A.dims[1];
+            if (QD != B->dims[3]) fail(N, "q and k have head dimension " + std::to_string(QD) + ", v has " + std::to_string(B->dims[3]));
+            Val V = A;
+            V.attV = B->v;
+            V.chain = A.chain + "+" + B->chain;
+            return put(V, kFormHeadOut, {kBatch, A.dims[1], 81, B->dims[3]});
+        }
+        fail(N, "MatMul of " + dimsStr(A.dims) + " and " + dimsStr(B->dims) + " is outside the attention pattern (q k^T, then softmax x v; DESIGN.md section 13.3)");
+    }
+    // Mul / Div / Add with a constant
+    const bool AR = FA >= kFormTok4;
+    const Val& T = AR ? A : *B;
+    const Val& Cst = AR ? *B : A;
+    if (Cst.runtime) fail(N, "the other operand of " + Op + " on " + dimsStr(T.dims) + " is computed at run time: only constants enter the attention pattern");
+    interior(N, AR ? 0 : 1);
+    if (Op == "Mul" || Op == "Div") {
+        if (Cst.count() != 1) fail(N, "only a scalar constant scales the attention pattern's tensors");
+        if (Op == "Div" && !AR) fail(N, "a constant divided by " + dimsStr(T.dims) + " is outside the attention pattern");
+        if (T.form != kFormTok4 && T.form != kFormHeads && T.form != kFormHeadsT && T.form != kFormScores)
+            fail(N, Op + " on " + dimsStr(T.dims) + " is outside the attention pattern");
+        const double S = Op == "Mul" ? Cst.at(0) : 1.0 / Cst.at(0);
+        Val V = T;
+        V.scale *= S;
+        for (double& Bv : V.bias) Bv *= S;
+        return put(V, T.form, T.dims);
+    }
+    // Add: a constant bias on the scores
+    if (T.form != kFormScores) fail(N, "Add on " + dimsStr(T.dims) + " is outside the attention pattern (a constant bias is added to the scores)");
+    const int64_t H = T.dims[1];
+    std::vector<int64_t> CD = Cst.dims;
+    if (CD.size() == 4 && CD[0] == 1) CD.erase(CD.begin());
+    const bool PerHead = CD == std::vector<int64_t>{H, 81, 81};
+    if (!PerHead && CD != std::vector<int64_t>{81, 81} && CD != std::vector<int64_t>{1, 81, 81})
+        fail(N, "an attention bias of shape " + dimsStr(Cst.dims) + ": [H,81,81], [1,H,81,81] or [81,81] only");
+    Val V = T;
+    if (V.bias.empty()) V.bias.assign((size_t)H * 81 * 81, 0.0);
+    for (size_t J = 0; J < V.bias.size(); ++J) V.bias[J] += Cst.at(PerHead ? J : J % (81 * 81));
+    return put(V, kFormScores, T.dims);
+}
+
+// The exact GELU as the exporter writes it, x * (1 + erf(x / sqrt(2))) * 0.5 over five nodes, becomes one Gelu node
+// (then an activation like any other: it fuses into a dense epilogue).
+void Planner::rewriteGelu() {
+    std::map<std::string, int> Cnt;
+    std::map<std::string, size_t> Producer;
+    for (size_t K = 0; K < Nodes.size(); ++K) {
+        if (Skip[K]) continue;
+        for (const std::string& I : Nodes[K].In) ++Cnt[I];
+        for (const std::string& O : Nodes[K].Out) Producer[O] = K;
+    }
+    auto scalar = [&](const std::string& T, double* V) {
+        auto It = G.Inits.find(T);
+        if (It == G.Inits.end() || !It->second.IsFloat || It->second.F.size() != 1) return false;
+        *V = It->second.F[0];
+        return true;
+    };
+    // the node producing T when it has op `Op`, one consumer, and T is no graph output
+    auto inner = [&](const std::string& T, const char* OpName) -> int {
+        auto It = Producer.find(T);
+        if (It == Producer.end() || Nodes[It->second].Op != OpName || Cnt[T] != 1 || Outputs.count(T)) return -1;
+        return (int)It->second;
+    };
+    // a two-input node as (runtime operand, scalar constant)
+    auto withScalar = [&](const Node& N, std::string* T, double* V) {
+        if (N.In.size() != 2) return false;
+        for (int Side = 0; Side < 2; ++Side)
+            if (scalar(N.In[(size_t)Side], V)) { *T = N.In[(size_t)(1 - Side)]; return true; }
+        return false;
+    };
+    for (size_t K = 0; K < Nodes.size(); ++K) {
+        Node& Half = Nodes[K];
+        std::string T1, T2, T3, Xs;
+        double V = 0;
+        if (Skip[K] || Half.Op != "Mul" || !withScalar(Half, &T1, &V) || V != 0.5) continue;
+        const int IM = inner(T1, "Mul"); // x * (erf + 1)
+        if (IM < 0 || Nodes[(size_t)IM].In.size() != 2) continue;
+        for (int Side = 0; Side < 2; ++Side) {
+            const std::string& X = Nodes[(size_t)IM].In[(size_t)Side];
+            const int IA = inner(Nodes[(size_t)IM].In[(size_t)(1 - Side)], "Add");
+            if (IA < 0 || !withScalar(Nodes[(size_t)IA], &T2, &V) || V != 1.0) continue;
+            const int IE = inner(T2, "Erf");
+            if (IE < 0 || Nodes[(size_t)IE].In.size() != 1) continue;
+            const int ID = inner(Nodes[(size_t)IE].In[0], "Div");
+            const int IS = inner(Nodes[(size_t)IE].In[0], "Mul");
+            const int IX = ID >= 0 ? ID : IS;
+            if (IX < 0 || !withScalar(Nodes[(size_t)IX], &T3, &V) || T3 != X) continue;
+            if (ID >= 0 && (Nodes[(size_t)ID].In[0] != X || std::fabs(V - std::sqrt(2.0)) > 1e-6)) continue;
+            if (ID < 0 && std::fabs(V - std::sqrt(0.5)) > 1e-6) continue;
+            Xs = X;
+            for (int I : {IM, IA, IE, IX}) {
+                Skip[(size_t)I] = true;
+                Half.Name = Nodes[(size_t)I].Name + "+" + Half.Name;
+            }
+            break;
+        }
+        if (Xs.empty()) continue;
+        Half.Op = "Gelu";
+        Half.In = {Xs};
+        Cnt.clear(); // the counts the next candidate sees
+        for (size_t J = 0; J < Nodes.size(); ++J) {
+            if (Skip[J]) continue;
+            for (const std::string& I : Nodes[J].In) ++Cnt[I];
+        }
+    }
 }
 
 // ---- the plan ----------------------------------------------------------------------------------------------------
@@ -757,12 +1191,16 @@ void Planner::run() {
             }
         }
     }
+    rewriteGelu();
     for (size_t K = 0; K < Nodes.size(); ++K) {
         if (Skip[K]) continue;
         const Node& N = Nodes[K];
-        if (!opSet().count(N.Op) && N.Op != "Swish") fail(N, "op '" + N.Op + "' is outside the supported op set (DESIGN.md section 13)");
+        if (!opSet().count(N.Op) && N.Op != "Swish" && N.Op != "Gelu") fail(N, "op '" + N.Op + "' is outside the supported op set (DESIGN.md section 13)");
         for (const std::string& I : N.In)
-            if (!I.empty()) ++Uses[I];
+            if (!I.empty()) {
+                ++Uses[I];
+                if (N.Op == "Shape") ++ShapeUses[I];
+            }
     }
     for (const std::string& O : G.Outputs) ++Uses[O];
 
@@ -827,23 +1265,40 @@ void Planner::run() {
             continue;
         }
         const Val& X = get(N, 0);
-        if (Op == "Conv" || Op == "Gemm" || Op == "MatMul") {
+        if (formView(N) || attentionOp(N)) continue;
+        // [N,C,81] and the 4-D tensors exist only inside the patterns the two calls above follow
+        for (size_t J = 0; J < N.In.size(); ++J) {
+            if (N.In[J].empty()) continue;
+            const Val& I = Vals.at(N.In[J]);
+            if (I.runtime && I.form >= kFormChan3)
+                fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " is consumed outside the token-view and attention patterns (DESIGN.md section 13.3)");
+        }
+        if (Op == "Softmax") {
+            fail(N, "Softmax on " + dimsStr(X.dims) + ": only the softmax over the keys of the attention pattern, on [N,H,81,81] scores, is supported");
+        } else if (Op == "Transpose") {
+            fail(N, "Transpose of " + dimsStr(X.dims) + " with perm " + dimsStr(N.attrInts("perm", {})) + " is outside the token-view and attention patterns");
+        } else if (Op == "LayerNormalization") {
+            layerNorm(N);
+        } else if (Op == "Conv" || Op == "Gemm" || Op == "MatMul") {
             linear(N, K);
         } else if (isAct(Op) || isBinary(Op) || Op == "BatchNormalization") {
             if (Op == "BatchNormalization" && !X.runtime) fail(N, "expected a runtime input");
             if (isBinary(Op) && !get(N, 0).runtime && !get(N, 1).runtime) fail(N, "constant operands only");
             elementwise(N);
         } else if (Op == "GlobalAveragePool" || Op == "ReduceMean") {
-            if (X.flatOfSpatial || !isSpatialDims(X.dims)) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
+            const bool Tok = X.form == kFormToken && Op == "ReduceMean";
+            if (!Tok && (X.flatOfSpatial || !isSpatialDims(X.dims))) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
             bool Keep = true;
             if (Op == "ReduceMean") {
                 std::vector<int64_t> Axes = has(N, 1) ? ints(N, 1, "axes") : N.attrInts("axes", {});
-                for (int64_t& A : Axes) if (A < 0) A += 4;
+                for (int64_t& A : Axes) if (A < 0) A += Tok ? 3 : 4;
                 std::sort(Axes.begin(), Axes.end());
-                if (Axes != std::vector<int64_t>{2, 3}) fail(N, "ReduceMean over axes {2,3} only");
+                if (Tok ? Axes != std::vector<int64_t>{1} : Axes != std::vector<int64_t>{2, 3})
+                    fail(N, "ReduceMean over the squares only: axes {2,3} of [N,C,9,9], axis 1 of a token tensor");
                 Keep = N.attrI("keepdims", 1) != 0;
+                if (Tok && Keep) fail(N, "ReduceMean of a token tensor with keepdims = 0 only");
             }
-            const int C = (int)X.dims[1];
+            const int C = Tok ? (int)X.dims[2] : (int)X.dims[1];
             Launch L;
             L.kind = kLaunchMean;
             L.name = N.Name;
@@ -853,6 +1308,8 @@ void Planner::run() {
             V.v = L.out;
             emit(L);
             Vals[N.Out[0]] = V;
+        } else if (X.form == kFormToken && Op != "Slice" && Op != "Identity") {
+            fail(N, "op '" + Op + "' is not supported on a token tensor " + dimsStr(X.dims));
         } else if (Op == "Flatten" || Op == "Reshape" || Op == "Squeeze" || Op == "Unsqueeze" || Op == "Identity") {
             // an open elementwise group read only here stays open: the reshaped tensor is its new result
             // (a [N,C,9,9] group that becomes [N,C*81] is emitted first: the flattened view reads its buffer)
@@ -948,6 +1405,7 @@ void Planner::run() {
             for (size_t J = 0; J < N.In.size(); ++J) {
                 const Val& V = get(N, J);
                 if (!V.runtime) fail(N, "Concat of a runtime tensor and a constant");
+                if (V.form != kFormPlain) fail(N, "Concat of a token tensor " + dimsStr(V.dims));
                 const bool VS = !V.flatOfSpatial && isSpatialDims(V.dims);
                 if (J == 0) Sp = VS;
                 if (VS != Sp) fail(N, "Concat of [N,C,9,9] and flat tensors");
@@ -974,10 +1432,11 @@ void Planner::run() {
             if (St.size() != En.size() || Axes.size() != St.size() || Sp.size() != St.size()) fail(N, "malformed Slice");
             Val V = Src;
             V.producer = N.Name;
+            const int64_t ChanAxis = Src.form == kFormToken ? 2 : 1;
             for (size_t J = 0; J < Axes.size(); ++J) {
                 int64_t A = Axes[J] < 0 ? Axes[J] + (int64_t)Src.dims.size() : Axes[J];
                 if (Sp[J] != 1) fail(N, "Slice with a step other than 1");
-                if (A == 1) {
+                if (A == ChanAxis) {
                     const int64_t Len = Src.v.C;
                     int64_t S = St[J] < 0 ? St[J] + Len : St[J], E = En[J] < 0 ? En[J] + Len : En[J];
                     S = std::max<int64_t>(0, std::min(S, Len));
@@ -985,10 +1444,10 @@ void Planner::run() {
                     if (E == S) fail(N, "empty slice");
                     V.v.offset += (int)S;
                     V.v.C = (int)(E - S);
-                    V.dims[1] = E - S;
+                    V.dims[(size_t)ChanAxis] = E - S;
                 } else {
                     const int64_t Dim = A < (int64_t)Src.dims.size() ? Src.dims[(size_t)A] : 1;
-                    if (St[J] != 0 || (Dim != kBatch && En[J] < Dim)) fail(N, "Slice along an axis other than 1");
+                    if (St[J] != 0 || (Dim != kBatch && En[J] < Dim)) fail(N, "Slice along an axis other than the channels");
                 }
             }
             Vals[N.Out[0]] = V;
@@ -1051,6 +1510,8 @@ void Planner::assignBuffers() {
         const Launch& L = P.launches[(size_t)I];
         use(L.in, I);
         use(L.res, I);
+        use(L.attK, I);
+        use(L.attV, I);
         for (const EltSrc& S : L.srcs) if (S.mode == kSrcSame || S.mode == kSrcBoard) use(S.v, I);
         for (const CopySeg& S : L.segs) use(S.v, I);
         use(L.out, I);
@@ -1091,6 +1552,8 @@ void Planner::assignBuffers() {
     for (Launch& L : P.launches) {
         map(L.in);
         map(L.res);
+        map(L.attK);
+        map(L.attV);
         map(L.out);
         for (EltSrc& S : L.srcs) if (S.mode == kSrcSame || S.mode == kSrcBoard) map(S.v);
         for (CopySeg& S : L.segs) map(S.v);

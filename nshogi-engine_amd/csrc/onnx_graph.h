@@ -4,6 +4,8 @@
 //
 // Layout of every runtime tensor (the library's board-major, channel-innermost layout):
 //   spatial [N,C,9,9]           -> [row = board * 81 + square][stride] floats
+//   token [N,81,C]              -> the same rows under another logical shape: a transformer's token tensor over the
+//                                  81 squares is the spatial layout, so flatten(2).transpose(1,2) costs no launch
 //   flat [N,C] / [N,C,1,1] / [N] -> [row = board][stride] floats
 // stride = C rounded up to 16 (the conv kernel's K chunk); channels C..stride-1 are written as zero by every kernel.
 // A view names a buffer plus a channel offset, so `Slice` along the channel axis costs no launch.
@@ -25,7 +27,7 @@ constexpr int kMaxEltCode = 32; // instructions of one fused elementwise launch
 constexpr int kMaxEltRegs = 16;
 constexpr int kMaxCopySegs = 8; // sources of one channel concat
 
-enum Act { kActNone = 0, kActRelu, kActSigmoid, kActTanh, kActSwish, kActSoftplus };
+enum Act { kActNone = 0, kActRelu, kActSigmoid, kActTanh, kActSwish, kActSoftplus, kActErf, kActGelu }; // kActGelu: exact (erf)
 
 // A runtime tensor as a launch sees it.  buf: -1 = the plane buffer (graph input), >= 0 = activation buffer.
 struct View {
@@ -47,6 +49,7 @@ enum EltMode {
     kSrcBoard,      // flat view broadcast over squares: (row / 81, c)
     kSrcChannel,    // constant per channel: weights[constOff + c]
     kSrcScalar,     // constant: `scalar`
+    kSrcSquareChannel, // constant per (square, channel), a learned positional embedding: weights[constOff + (row % 81) * C + c]
 };
 struct EltSrc {
     int mode = kSrcScalar;
@@ -55,7 +58,8 @@ struct EltSrc {
     float scalar = 0.f;
 };
 
-enum LaunchKind { kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten };
+enum LaunchKind { kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention };
+constexpr int kMaxHeadDim = 64; // channels per attention head (a multiple of 4)
 struct CopySeg { View v; int dstOff = 0; };
 
 struct Launch {
@@ -77,6 +81,15 @@ struct Launch {
     int eltOut = 0;  // the register stored
     // kLaunchMean / kLaunchFlatten: `in`; kLaunchConcat: segments
     std::vector<CopySeg> segs;
+    // kLaunchLayerNorm: over the channels of each row of `in` (token rows or boards); gamma at wOff, beta at biasOff
+    float eps = 0.f;
+    // kLaunchAttention: softmax(scale * q k^T + bias) v per (board, head) over the 81 squares.  q = `in`, k, v: token
+    // views of heads * headDim channels; bias (hasBias): [heads][81][81] at biasOff; out: token rows, head h at
+    // channels h * headDim
+    View attK, attV;
+    int heads = 0, headDim = 0;
+    float scale = 1.f;
+    bool hasBias = false;
 };
 
 struct GraphPlan {
@@ -90,6 +103,7 @@ struct GraphPlan {
     // reported by nsg_get_graph_info / nsg_inspect_onnx
     int nodes = 0;
     int convLaunches = 0;
+    int attentionLaunches = 0;
     uint64_t params = 0;
     double flopsPerPosition = 0.0;
     size_t activationBytesPerPosition = 0;

@@ -3,11 +3,17 @@
     python scripts/graph_bench.py [--out profiles/graph/graph_bench.json] [--batches 1,64,512]
     python scripts/graph_bench.py --trace      # one shape for `rocprofv3 --kernel-trace --stats`
     python scripts/graph_bench.py --summarize DIR/run_results.db   # per-kernel times and the conv's share of peak
+    python scripts/graph_bench.py --attention [--out profiles/graph/attention_bench.json]   # the transformer row
+    python scripts/graph_bench.py --trace-attention      # one shape of it for `rocprofv3 --kernel-trace --stats`
+    python scripts/graph_bench.py --summarize-attention DIR/run_results.db   # each kernel's share of that forward
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
 time with PyTorch's exporter.  evals/s = positions / wall time of `iters` computeBlocking calls after a warm-up.
 Also the SE net's load time (nsg_load on the .onnx file, planning and upload included).
+
+--attention: a pre-LN transformer over the 81 squares (tests/golden/make_onnx_attention_golden.py's PreNet with 8
+blocks, F = 256, H = 8 heads of d = 32, FFN width 1024), exported at run time, on the general path.
 """
 import argparse
 import importlib
@@ -33,6 +39,14 @@ def se_onnx(path):
     torch.manual_seed(5)
     net = mk.randomize_bn(mk.SENet(C=86, F=256, blocks=20, VC=32, VH=256), 13).eval()
     mk.export_model(net, path, 86, True)
+
+
+def attention_onnx(path):
+    import torch
+    import make_onnx_attention_golden as mk
+    torch.manual_seed(6)
+    net = mk.randomize(mk.PreNet(C=86, F=256, H=8, ffn=1024, VH=256, blocks=8), 14).eval()
+    mk.export_model(net, path)
 
 
 def rate(nsg, path, batch, prec="fp32", force=False, iters=50, warmup=5):
@@ -82,18 +96,63 @@ def summarize(db):
           f"{(40 * fl_main + fl_stem) / tot / F32_MFMA_PEAK:.3f} of peak")
 
 
+def summarize_attention(db):
+    """Each kernel's share of the transformer's forward (a --trace-attention run), and the attention + LayerNorm time
+    against the dense launches' (graphConv<1>)."""
+    import sqlite3
+    c = sqlite3.connect(db)
+    rows = list(c.execute("select name, count(*), sum(end-start), avg(end-start) from kernels group by name "
+                          "order by sum(end-start) desc"))
+    total = sum(r[2] for r in rows)
+    print(f"{'kernel':60s} {'calls':>6s} {'total ms':>10s} {'avg us':>9s} {'share':>7s}")
+    group = {"dense": 0, "attention": 0, "layernorm": 0}
+    for n, k, t, a in rows:
+        short = n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        print(f"{short:60s} {k:6d} {t / 1e6:10.2f} {a / 1e3:9.1f} {t / total:7.3f}")
+        for key, pat in (("dense", "graphConv<1>"), ("attention", "graphAttention"), ("layernorm", "graphLayerNorm")):
+            if pat in n:
+                group[key] += t
+    print()
+    print("share of all kernel time: " + ", ".join(f"{k} {v / total:.3f}" for k, v in group.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "graph", "graph_bench.json"))
     ap.add_argument("--batches", default="1,64,512")
     ap.add_argument("--trace", action="store_true", help="only the forced 20x256 general path at B=512, 20 forwards")
     ap.add_argument("--summarize", metavar="DB", help="summarise the rocprofv3 database of a --trace run")
+    ap.add_argument("--attention", action="store_true", help="the 8-block F=256 H=8 transformer on the general path")
+    ap.add_argument("--trace-attention", action="store_true", help="only that transformer at B=512, 13 forwards")
+    ap.add_argument("--summarize-attention", metavar="DB", help="summarise the rocprofv3 database of a --trace-attention run")
     a = ap.parse_args()
     if a.summarize:
         summarize(a.summarize)
         return
+    if a.summarize_attention:
+        summarize_attention(a.summarize_attention)
+        return
     nsg = importlib.import_module("nshogi-engine_amd")
     tmp = tempfile.mkdtemp()
+    if a.attention or a.trace_attention:
+        att = os.path.join(tmp, "attention_8x256.onnx")
+        attention_onnx(att)
+        if a.trace_attention:
+            r, info = rate(nsg, att, TRACE_BATCH, iters=10, warmup=3)
+            print(json.dumps({"trace_evals_per_s": r, "flops_per_position": info["flops_per_position"]}))
+            return
+        row = {}
+        for b in [int(b) for b in a.batches.split(",")]:
+            r, info = rate(nsg, att, b, iters=20 if b >= 256 else 50)
+            row[str(b)] = round(r, 1)
+            row.update(path=info["path"], launches=info["launches"], attention_launches=info["attention_launches"],
+                       flops_per_position=info["flops_per_position"])
+        print("attention_8x256_general", json.dumps(row), flush=True)
+        out = a.out.replace("graph_bench.json", "attention_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump({"rows": {"attention_8x256_general": row}}, f, indent=1)
+        return
     fam = os.path.join(tmp, "family_20x256.onnx")
     family_onnx(nsg, fam)
     if a.trace:
