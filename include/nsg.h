@@ -105,7 +105,9 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    precision (nsg_set_precision);
  *  - otherwise the general graph path, when the model
  *    is built only from its closed op set (section 13.2): convolutional nets
- *    with SE / global pooling, and transformer or conv-plus-attention nets
+ *    with SE / global pooling, whose stride-1 convs keep the 9x9 board with
+ *    odd kernels up to 9x9 (1x9 and 9x1 too), dilations while a tap reaches
+ *    at most 4 squares past the edge, group 1 or depthwise; and transformer or conv-plus-attention nets
  *    over the 81 squares as tokens [N,81,C] -- dense layers, LayerNorm, exact
  *    GELU, a learned positional embedding and the multi-head attention
  *    pattern of section 13.3, which runs as one launch per block.  A general graph always runs in

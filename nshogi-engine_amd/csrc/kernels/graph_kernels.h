@@ -20,12 +20,27 @@ struct DevView {
 };
 
 // Implicit-GEMM convolution on the f32 MFMA (v_mfma_f32_16x16x4_f32): M = groups x 81 rows, N = output channels,
-// K = taps x cinPad.  taps 9: a 3x3 conv of `groups` boards; taps 1: a 1x1 conv, or a dense layer when the rows are
+// K = taps x cinPad.  taps 9: a 3x3 conv (dilation 1) of `groups` boards; taps 1: a 1x1 conv, or a dense layer when the rows are
 // boards (then `groups` = ceil(boards / 81) and `rows` masks the last group).  w: packed [coutTiles][cinPad/16][taps]
 // [16][64]; bias [coutTiles * 64].  y = act(acc + bias[c] (+ res)), written for rows < `rows`, channels < out stride.
 hipError_t launchGraphConv(const float* in, int inStride, const float* w, const float* bias, DevView res,
                            float* out, int outStride, int cout, int cinPad, int coutTiles, int taps, int groups,
                            long rows, int act, hipStream_t stream);
+
+// The same conv for every other geometry: kh x kw taps (odd, at most 9), dilations dh, dw, a halo dh (kh-1)/2 by
+// dw (kw-1)/2 of at most kMaxConvHalo squares; `boards` boards of 81 rows.  w: packed [coutTiles][cinPad/16][kh * kw]
+// [16][64], taps row-major over (ky, kx).  The sum of an output element runs in launchGraphConv's order (chunk, tap,
+// channel): a 5x5 kernel whose outer ring is zero gives the bits of the 3x3 kernel at its centre.
+hipError_t launchGraphConvGeo(const float* in, int inStride, const float* w, const float* bias, DevView res,
+                              float* out, int outStride, int cout, int cinPad, int coutTiles, int kh, int kw, int dh,
+                              int dw, int boards, int act, hipStream_t stream);
+
+// Depthwise conv of the same geometries on the VALU: y[c] = act(sum over taps of x[c] w[c][tap] + bias[c] (+ res)), one
+// fmaf chain per (square, channel) in row-major tap order.  w: [outStride/16][kh * kw][16]; bias [outStride];
+// outStride = C rounded up to 16, the input's rows at least as wide.
+hipError_t launchGraphDepthwise(const float* in, int inStride, const float* w, const float* bias, DevView res,
+                                float* out, int outStride, int C, int kh, int kw, int dh, int dw, int boards, int act,
+                                hipStream_t stream);
 
 // Fused elementwise chain (the program of onnx_graph.h's EltInstr / EltSrc) over `rows` rows.
 struct EltArgs {

@@ -895,8 +895,15 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
             gr::DevView res;
             if (L.res.buf != -2) res = dv(L.res);
             const int groups = L.dense ? (B + 80) / 81 : B;
-            NSG_HIP(gr::launchGraphConv(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out), L.out.stride,
-                                        L.out.C, L.cinPad, L.coutTiles, L.taps, groups, rowsOf(L.out), L.act, s));
+            if (L.depthwise)
+                NSG_HIP(gr::launchGraphDepthwise(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out),
+                                                 L.out.stride, L.out.C, L.kh, L.kw, L.dh, L.dw, B, L.act, s));
+            else if (L.kh == L.kw && (L.kh == 1 || L.kh == 3) && L.dh == 1 && L.dw == 1)
+                NSG_HIP(gr::launchGraphConv(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out), L.out.stride,
+                                            L.out.C, L.cinPad, L.coutTiles, L.taps, groups, rowsOf(L.out), L.act, s));
+            else
+                NSG_HIP(gr::launchGraphConvGeo(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out),
+                                               L.out.stride, L.out.C, L.cinPad, L.coutTiles, L.kh, L.kw, L.dh, L.dw, B, L.act, s));
             if (prof && ++convs == P.convLaunches) NSG_HIP(hipEventRecord(e[2], s));
             break;
         }

@@ -490,28 +490,60 @@ void Planner::linear(const Node& N, size_t Index) {
     const bool Dense = N.Op != "Conv";
     const bool Tok = X.form == kFormToken; // a Linear over tokens: the 1x1 form of the conv, rows = (board, square)
     if (Tok && N.Op != "MatMul") fail(N, "a token tensor " + dimsStr(X.dims) + " feeds MatMul, not " + N.Op);
-    int Cin = 0, Cout = 0, K = 1;
-    std::vector<double> W, Bias; // W[cout][cin][taps]
+    int Cin = 0, Cout = 0, KH = 1, KW = 1, DH = 1, DW = 1;
+    int CinW = 0;           // input channels per output channel in W: Cin, or 1 for a depthwise conv
+    bool Depthwise = false;
+    std::vector<double> W, Bias; // W[cout][CinW][taps], taps row-major over (ky, kx)
     std::string Name = N.Name;
     if (!Dense) {
         const Val& Wt = host(N, 1, "the weight");
-        if (Wt.isInt || Wt.dims.size() != 4 || Wt.dims[2] != Wt.dims[3] || (Wt.dims[2] != 1 && Wt.dims[2] != 3))
-            fail(N, "only 1x1 and 3x3 float weights");
-        K = (int)Wt.dims[2];
-        const int64_t Pad = K / 2;
-        bool Ok = N.attrI("group", 1) == 1;
-        for (int64_t S : N.attrInts("strides", {1, 1})) Ok = Ok && S == 1;
-        for (int64_t D : N.attrInts("dilations", {1, 1})) Ok = Ok && D == 1;
+        if (Wt.isInt || Wt.dims.size() != 4) fail(N, "expected a 4-D float weight [Cout,Cin/group,kh,kw]");
+        const int64_t Kh64 = Wt.dims[2], Kw64 = Wt.dims[3];
+        const std::string KStr = std::to_string(Kh64) + "x" + std::to_string(Kw64);
+        for (int64_t S : N.attrInts("strides", {1, 1}))
+            if (S != 1) fail(N, "stride " + std::to_string(S) + ": only stride 1 (the output stays 9x9)");
+        if (Kh64 < 1 || Kw64 < 1 || Kh64 > 9 || Kw64 > 9 || Kh64 % 2 == 0 || Kw64 % 2 == 0)
+            fail(N, "a " + KStr + " kernel: only odd kernel sizes from 1 to 9 each way");
+        const std::vector<int64_t> Dil = N.attrInts("dilations", {1, 1});
+        if (Dil.size() != 2 || Dil[0] < 1 || Dil[1] < 1) fail(N, "two dilations of at least 1 expected");
+        KH = (int)Kh64;
+        KW = (int)Kw64;
+        DH = KH == 1 ? 1 : (int)std::min<int64_t>(Dil[0], 64); // a dilation along an axis of one tap means nothing
+        DW = KW == 1 ? 1 : (int)std::min<int64_t>(Dil[1], 64);
+        const int Hy = DH * (KH - 1) / 2, Hx = DW * (KW - 1) / 2;
+        if (Hy > kMaxConvHalo || Hx > kMaxConvHalo)
+            fail(N, "a " + KStr + " kernel at dilation " + std::to_string(Dil[0]) + "x" + std::to_string(Dil[1]) + " reaches " +
+                        std::to_string(std::max(Hy, Hx)) + " squares past the edge: the halo is at most " + std::to_string(kMaxConvHalo));
+        if (N.Attrs.count("auto_pad")) fail(N, "auto_pad: only explicit pads");
         const std::vector<int64_t> Pads = N.attrInts("pads", {0, 0, 0, 0});
-        Ok = Ok && Pads.size() == 4;
-        for (int64_t P1 : Pads) Ok = Ok && P1 == Pad;
-        if (N.Attrs.count("auto_pad")) Ok = false;
-        if (!Ok) fail(N, "only stride 1, dilation 1, group 1 and 'same' padding (explicit pads)");
+        if (Pads != std::vector<int64_t>{Hy, Hx, Hy, Hx}) {
+            std::string Ps;
+            for (int64_t P1 : Pads) Ps += (Ps.empty() ? "" : ",") + std::to_string(P1);
+            fail(N, "pads [" + Ps + "] do not keep the 9x9 board: a " + KStr + " kernel at dilation " + std::to_string(DH) + "x" +
+                        std::to_string(DW) + " needs [" + std::to_string(Hy) + "," + std::to_string(Hx) + "," + std::to_string(Hy) + "," + std::to_string(Hx) + "]");
+        }
         Cout = (int)Wt.dims[0];
-        Cin = (int)Wt.dims[1];
         if (X.flatOfSpatial || !isSpatialDims(X.dims)) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
+        const int64_t Group = N.attrI("group", 1);
+        if (Group == 1) {
+            Cin = (int)Wt.dims[1];
+        } else {
+            // depthwise only: group = Cin = Cout, weight [C,1,kh,kw]
+            const int64_t XC = X.dims[1];
+            if (Group != XC)
+                fail(N, "group " + std::to_string(Group) + " on " + std::to_string(XC) + " input channels: only group 1 or a depthwise conv (group = input channels = output channels)");
+            if (Wt.dims[1] != 1) fail(N, "group " + std::to_string(Group) + " with a weight of " + std::to_string(Wt.dims[1]) + " channels per group: a depthwise weight is [C,1,kh,kw]");
+            if (Cout != (int)XC)
+                fail(N, "a depthwise conv with channel multiplier " + std::to_string(XC > 0 ? Cout / XC : 0) + " (" + std::to_string(XC) + " -> " +
+                            std::to_string(Cout) + " channels): only multiplier 1");
+            Depthwise = true;
+            Cin = (int)XC;
+            CinW = 1;
+        }
         if ((int)X.dims[1] != Cin)
             fail(N, "the weight expects " + std::to_string(Cin) + " input channels, '" + N.In[0] + "' has " + std::to_string(X.dims[1]));
+        if (!Depthwise) CinW = Cin;
+        if (Wt.f.size() != (size_t)Cout * CinW * KH * KW) fail(N, "the weight's data does not match its shape");
         W.assign(Wt.f.begin(), Wt.f.end());
         Bias.assign((size_t)Cout, 0.0);
         if (has(N, 2)) {
@@ -530,6 +562,7 @@ void Planner::linear(const Node& N, size_t Index) {
         }
         Cout = (int)(TransB ? Wt.dims[0] : Wt.dims[1]);
         Cin = (int)(TransB ? Wt.dims[1] : Wt.dims[0]);
+        CinW = Cin;
         const int XC = Tok ? (int)X.dims[2] : X.flatOfSpatial ? X.v.C * 81 : flatC(X.dims);
         if (X.dims.size() != 2 && !X.flatOfSpatial && !Tok) fail(N, "input " + dimsStr(X.dims) + " is not 2-D [N,K]");
         if (XC != Cin) fail(N, "the weight expects K = " + std::to_string(Cin) + ", '" + N.In[0] + "' has " + std::to_string(XC));
@@ -544,7 +577,7 @@ void Planner::linear(const Node& N, size_t Index) {
             for (int C = 0; C < Cout; ++C) Bias[(size_t)C] = B.at(B.count() == 1 ? 0 : (size_t)C);
         }
     }
-    const int Taps = K * K;
+    const int Taps = KH * KW;
     std::vector<int64_t> Dims = Tok ? std::vector<int64_t>{kBatch, 81, Cout}
                                     : Dense ? std::vector<int64_t>{kBatch, Cout} : std::vector<int64_t>{kBatch, Cout, 9, 9};
     const int ChanAxis = Tok ? 2 : 1;
@@ -566,7 +599,7 @@ void Planner::linear(const Node& N, size_t Index) {
                 const double Gm = Vals.at(C->In[1]).at((size_t)O), Bt = Vals.at(C->In[2]).at((size_t)O);
                 const double Mn = Vals.at(C->In[3]).at((size_t)O), Vr = Vals.at(C->In[4]).at((size_t)O);
                 const double S = Gm / std::sqrt(Vr + Eps);
-                for (size_t J = (size_t)O * Cin * Taps; J < (size_t)(O + 1) * Cin * Taps; ++J) W[J] *= S;
+                for (size_t J = (size_t)O * CinW * Taps; J < (size_t)(O + 1) * CinW * Taps; ++J) W[J] *= S;
                 Bias[(size_t)O] = (Bias[(size_t)O] - Mn) * S + Bt;
             }
         } else if (C->Op == "Add" && C->In.size() == 2) {
@@ -600,14 +633,29 @@ void Planner::linear(const Node& N, size_t Index) {
     L.kind = kLaunchConv;
     L.name = Name;
     L.dense = Dense && !Tok;
+    L.depthwise = Depthwise;
     L.taps = Taps;
+    L.kh = KH;
+    L.kw = KW;
+    L.dh = DH;
+    L.dw = DW;
     L.in = plain(N.In[0], N.Name + " (input copy)");
     L.cinPad = roundUp(Cin, kChunk);
-    L.coutTiles = (Cout + kCoutTile - 1) / kCoutTile;
+    L.coutTiles = Depthwise ? 0 : (Cout + kCoutTile - 1) / kCoutTile;
     L.act = Act;
     L.res.buf = kNoRes;
     if (!Res.empty()) L.res = ready(Res).v;
-    {   // packed [tile][chunk][tap][16][64], f32 of the double product (BatchNorm folded in double)
+    if (Depthwise) { // per-channel taps packed [chunk][tap][16], BatchNorm folded into them in double
+        const int Chunks = L.cinPad / kChunk;
+        std::vector<float> Pk((size_t)Chunks * Taps * kChunk, 0.f);
+        for (int C = 0; C < Cout; ++C)
+            for (int Tp = 0; Tp < Taps; ++Tp)
+                Pk[((size_t)(C / kChunk) * Taps + Tp) * kChunk + C % kChunk] = (float)W[(size_t)C * Taps + Tp];
+        L.wOff = addConst(Pk);
+        std::vector<float> Bf((size_t)L.cinPad, 0.f);
+        for (int O = 0; O < Cout; ++O) Bf[(size_t)O] = (float)Bias[(size_t)O];
+        L.biasOff = addConst(Bf);
+    } else {   // packed [tile][chunk][tap][16][64], f32 of the double product (BatchNorm folded in double)
         const int Chunks = L.cinPad / kChunk;
         std::vector<float> Pk((size_t)L.coutTiles * Chunks * Taps * kChunk * kCoutTile, 0.f);
         for (int T = 0; T < L.coutTiles; ++T)
@@ -626,7 +674,7 @@ void Planner::linear(const Node& N, size_t Index) {
         L.biasOff = addConst(Bf);
     }
     L.out = freshView(Cout, !L.dense);
-    P.flopsPerPosition += 2.0 * (L.dense ? 1 : 81) * Taps * (double)Cin * Cout;
+    P.flopsPerPosition += 2.0 * (L.dense ? 1 : 81) * Taps * (double)CinW * Cout;
     Val V = runtimeVal(N, Dims, OutForm);
     V.v = L.out;
     V.producer = N.Name;

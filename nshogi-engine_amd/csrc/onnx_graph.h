@@ -22,6 +22,7 @@ namespace graph {
 
 constexpr int kChunk = 16;      // channel granule of every activation stride and of the conv kernel's K chunk
 constexpr int kCoutTile = 64;   // output channels per conv workgroup
+constexpr int kMaxConvHalo = 4; // squares a conv tap may reach past the board's edge (the LDS image is at most 17 x 17)
 constexpr int kMaxEltSrcs = 8;  // inputs of one fused elementwise launch
 constexpr int kMaxEltCode = 32; // instructions of one fused elementwise launch
 constexpr int kMaxEltRegs = 16;
@@ -66,14 +67,19 @@ struct Launch {
     int kind = kLaunchConv;
     std::string name; // the ONNX node(s) it runs
     View out;
-    // kLaunchConv: an implicit-GEMM conv (taps 9 or 1) or a dense layer (taps 1, rows = boards)
+    // kLaunchConv: an implicit-GEMM conv (taps = kh x kw, row-major over (ky, kx)), a dense layer (taps 1, rows =
+    // boards) or a depthwise conv.  A tap reads the square (ky - (kh-1)/2) * dh rows and (kx - (kw-1)/2) * dw columns
+    // away; the halo dh * (kh-1)/2 by dw * (kw-1)/2 is at most kMaxConvHalo each way.  1x1 and 3x3 at dilation 1 run
+    // on graphConv<1> / graphConv<9>, every other dense geometry on graphConvGeo, depthwise on graphDepthwise.
     View in, res;    // res.buf == -2: no residual
     bool dense = false;
+    bool depthwise = false; // group = Cin = Cout: per-channel taps, no sum over channels
     int taps = 9;
+    int kh = 3, kw = 3, dh = 1, dw = 1;
     int cinPad = 0;  // K = taps x cinPad
-    int coutTiles = 0;
-    size_t wOff = 0;    // packed weights [coutTiles][cinPad / 16][taps][16][64]
-    size_t biasOff = 0; // [coutTiles * 64]
+    int coutTiles = 0;  // depthwise: unused (0)
+    size_t wOff = 0;    // packed weights [coutTiles][cinPad / 16][taps][16][64]; depthwise: [cinPad / 16][taps][16]
+    size_t biasOff = 0; // [coutTiles * 64]; depthwise: [cinPad]
     int act = kActNone;
     // kLaunchElt
     std::vector<EltSrc> srcs;

@@ -1,15 +1,17 @@
 """Throughput of the general graph path against the specialised path, on the same network.
 
     python scripts/graph_bench.py [--out profiles/graph/graph_bench.json] [--batches 1,64,512]
-    python scripts/graph_bench.py --trace      # one shape for `rocprofv3 --kernel-trace --stats`
-    python scripts/graph_bench.py --summarize DIR/run_results.db   # per-kernel times and the conv's share of peak
+    python scripts/graph_bench.py --trace      # one shape of two nets for `rocprofv3 --kernel-trace --stats`
+    python scripts/graph_bench.py --summarize DIR/run_results.db   # per-kernel times and each conv kernel's share of peak
     python scripts/graph_bench.py --attention [--out profiles/graph/attention_bench.json]   # the transformer row
     python scripts/graph_bench.py --trace-attention      # one shape of it for `rocprofv3 --kernel-trace --stats`
     python scripts/graph_bench.py --summarize-attention DIR/run_results.db   # each kernel's share of that forward
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
-time with PyTorch's exporter.  evals/s = positions / wall time of `iters` computeBlocking calls after a warm-up.
+time with PyTorch's exporter; a geometry 20x256 net (tests/golden/make_onnx_geometry_golden.py's GeomBenchNet: a 5x5
+stem, four blocks of two 5x5 convs, sixteen depthwise 7x7 + pointwise blocks), exported the same way.  evals/s =
+positions / wall time of `iters` computeBlocking calls after a warm-up.
 Also the SE net's load time (nsg_load on the .onnx file, planning and upload included).
 
 --attention: a pre-LN transformer over the 81 squares (tests/golden/make_onnx_attention_golden.py's PreNet with 8
@@ -41,6 +43,14 @@ def se_onnx(path):
     mk.export_model(net, path, 86, True)
 
 
+def geometry_onnx(path):
+    import torch
+    import make_onnx_geometry_golden as mk
+    torch.manual_seed(7)
+    net = mk.randomize(mk.GeomBenchNet(C=86, F=256, blocks=20, VC=32, VH=256), 15).eval()
+    mk.export_model(net, path)
+
+
 def attention_onnx(path):
     import torch
     import make_onnx_attention_golden as mk
@@ -66,7 +76,9 @@ def rate(nsg, path, batch, prec="fp32", force=False, iters=50, warmup=5):
     return batch * iters / dt, info
 
 
-TRACE_BATCH, TRACE_FORWARDS = 512, 23  # --trace: 3 warm-up + 20 timed forwards of the 20x256 net at B = 512
+TRACE_BATCH, TRACE_FORWARDS = 512, 23  # --trace: 3 warm-up + 20 timed forwards of the 20x256 net at B = 512 ...
+GEOM_FORWARDS = 8                      # ... then 3 + 5 of the geometry net
+HBM_PEAK = 8.0e12  # bytes/s
 F32_MFMA_PEAK = 157.3e12  # FLOP/s at the 2.4 GHz peak clock (MI355X_MICROARCH): the run's clock is not sampled
 
 
@@ -94,6 +106,27 @@ def summarize(db):
     tot = sum(d) * 1e-9 / (len(d) / per_fwd)
     print(f"all 3x3 launches of a forward: {tot * 1e3:.2f} ms for {(40 * fl_main + fl_stem) / 1e9:.1f} GFLOP = "
           f"{(40 * fl_main + fl_stem) / tot / F32_MFMA_PEAK:.3f} of peak")
+    one = [r[0] for r in c.execute("select end-start from kernels where name like '%graphConv<1>%' order by start")]
+    one = one[:5 * (len(d) // per_fwd)]  # the family net's: two head convs and three dense layers per forward, run first
+    if one:
+        print(f"1x1 / dense launches of the family net (graphConv<1>): {len(one)} launches, avg {statistics.mean(one) / 1e3:.1f} us, "
+              f"total {sum(one) / 1e6:.2f} ms")
+    # the geometry net (GeomBenchNet): per forward a 5x5 stem and eight 5x5 256->256 convs on graphConvGeo, sixteen
+    # depthwise 7x7 convs of 256 channels on graphDepthwise
+    geo = [r[0] for r in c.execute("select end-start from kernels where name like '%graphConvGeo%' order by start")]
+    if geo:
+        main_geo = [geo[i] for i in range(len(geo)) if i % 9 != 0]
+        fl5 = 2.0 * TRACE_BATCH * 81 * 25 * 256 * 256
+        m5 = statistics.median(main_geo) * 1e-9
+        print(f"5x5 256->256 conv (graphConvGeo), B={TRACE_BATCH}: {fl5 / 1e9:.2f} GFLOP per launch, median {m5 * 1e6:.1f} us "
+              f"over {len(main_geo)} launches = {fl5 / m5 / 1e12:.1f} TFLOP/s = {fl5 / m5 / F32_MFMA_PEAK:.3f} of the f32 MFMA "
+              f"peak (3x3 on graphConv<9> in this run: {fl_main / m / F32_MFMA_PEAK:.3f})")
+    dwt = [r[0] for r in c.execute("select end-start from kernels where name like '%graphDepthwise%' order by start")]
+    if dwt:
+        by = 2.0 * TRACE_BATCH * 81 * 256 * 4  # one read and one write of the activation (no residual on this launch)
+        md = statistics.median(dwt) * 1e-9
+        print(f"depthwise 7x7, C=256, B={TRACE_BATCH}: {by / 1e6:.1f} MB per launch, median {md * 1e6:.1f} us over {len(dwt)} "
+              f"launches = {by / md / 1e12:.2f} TB/s = {by / md / HBM_PEAK:.3f} of {HBM_PEAK / 1e12:.0f} TB/s")
 
 
 def summarize_attention(db):
@@ -120,7 +153,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "graph", "graph_bench.json"))
     ap.add_argument("--batches", default="1,64,512")
-    ap.add_argument("--trace", action="store_true", help="only the forced 20x256 general path at B=512, 20 forwards")
+    ap.add_argument("--trace", action="store_true",
+                    help="only the forced 20x256 general path at B=512, 20 forwards, then the geometry net, 5 forwards")
     ap.add_argument("--summarize", metavar="DB", help="summarise the rocprofv3 database of a --trace run")
     ap.add_argument("--attention", action="store_true", help="the 8-block F=256 H=8 transformer on the general path")
     ap.add_argument("--trace-attention", action="store_true", help="only that transformer at B=512, 13 forwards")
@@ -158,14 +192,21 @@ def main():
     if a.trace:
         r, info = rate(nsg, fam, TRACE_BATCH, force=True, iters=TRACE_FORWARDS - 3, warmup=3)
         print(json.dumps({"trace_evals_per_s": r, "conv_flops_per_position": info["flops_per_position"]}))
+        geo = os.path.join(tmp, "geometry_20x256.onnx")
+        geometry_onnx(geo)
+        r, info = rate(nsg, geo, TRACE_BATCH, iters=GEOM_FORWARDS - 3, warmup=3)
+        print(json.dumps({"geometry_trace_evals_per_s": r, "flops_per_position": info["flops_per_position"]}))
         return
     se = os.path.join(tmp, "se_20x256.onnx")
     se_onnx(se)
+    geo = os.path.join(tmp, "geometry_20x256.onnx")
+    geometry_onnx(geo)
     res = {"batches": [int(b) for b in a.batches.split(",")], "rows": {}}
     for label, path, prec, force in (("family_20x256_general", fam, "fp32", True),
                                      ("family_20x256_specialised_fp32", fam, "fp32", False),
                                      ("family_20x256_specialised_f16m6", fam, "f16m6", False),
-                                     ("se_swish_20x256_general", se, "fp32", False)):
+                                     ("se_swish_20x256_general", se, "fp32", False),
+                                     ("geometry_20x256_general", geo, "fp32", False)):
         row = {}
         for b in res["batches"]:
             r, info = rate(nsg, path, b, prec, force, iters=20 if b >= 256 else 50)
