@@ -105,7 +105,9 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    precision (nsg_set_precision);
  *  - otherwise the general graph path, when the model
  *    is built only from its closed op set (section 13.2): convolutional nets
- *    with SE / global pooling, whose stride-1 convs keep the 9x9 board with
+ *    with SE / global mean and max pooling, stride-1 max and average pooling
+ *    that keeps the board, Split, and the clamp activations (relu6, hardswish,
+ *    hardsigmoid, Clip, LeakyRelu, PRelu, Max, Min, Abs, Neg), whose stride-1 convs keep the 9x9 board with
  *    odd kernels up to 9x9 (1x9 and 9x1 too), dilations while a tap reaches
  *    at most 4 squares past the edge, group 1 or depthwise; and transformer or conv-plus-attention nets
  *    over the 81 squares as tokens [N,81,C] -- dense layers, LayerNorm, exact

@@ -12,6 +12,7 @@
 // image grows to (9 + 2 hy) x (9 + 2 hx) positions and the chunk's weights are staged in groups of up to 8 taps.  Its
 // sum runs in graphConv's order -- chunk, tap (row-major), channel -- whatever the grouping.  graphDepthwise is the
 // per-channel conv on the VALU: the same image, one fmaf chain per (square, channel) in row-major tap order.
+#include "graph_act.h"
 #include "graph_kernels.h"
 
 namespace nsg {
@@ -25,19 +26,6 @@ constexpr int kThreads = 256;
 constexpr int kHalo = 121;    // 11 x 11 positions
 constexpr int kInStride = 17; // LDS floats per position: 16 channels + 1 (consecutive rows fall on distinct banks)
 constexpr int kWStride = 80;  // LDS floats per (tap, k) row of 64 outputs: the four k rows of a step on distinct banks
-
-__device__ inline float applyAct(float v, int act) {
-    switch (act) {
-    case kActRelu: return v > 0.f ? v : 0.f;
-    case kActSigmoid: return 1.f / (1.f + expf(-v));
-    case kActTanh: return tanhf(v);
-    case kActSwish: return v / (1.f + expf(-v));
-    case kActSoftplus: return v > 20.f ? v : log1pf(expf(v)); // torch's threshold
-    case kActErf: return erff(v);
-    case kActGelu: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); // exact GELU
-    default: return v;
-    }
-}
 
 template <int TAPS>
 __global__ __launch_bounds__(kThreads) void graphConv(const float* __restrict__ in, int inStride,

@@ -1,5 +1,5 @@
-// graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_ops.hip,
-// graph_attention.hip).
+// graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
+// graph_ops.hip, graph_attention.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -61,6 +61,17 @@ hipError_t launchGraphElt(const EltArgs& a, hipStream_t stream);
 
 // Mean over the 81 squares: [B*81][in] -> [B][outStride]
 hipError_t launchGraphMean(DevView in, float* out, int outStride, int boards, hipStream_t stream);
+
+// Max over the 81 squares, the same shapes; pad channels zero
+hipError_t launchGraphMax(DevView in, float* out, int outStride, int boards, hipStream_t stream);
+
+// MaxPool / AveragePool of kh x kw taps (odd, at most 9) at dilations dh, dw, stride 1, under the conv's halo rule: the
+// board stays 9x9.  mode: PoolMode.  `in` may start at any channel of its rows (an offset that is no multiple of 4 is
+// read with scalar loads); out: rows of outStride = C rounded up to 16, pad channels zero.  An average is the f32 sum
+// of the window in row-major tap order, the halo as zeros, then one division by kh * kw (kPoolAvgInclude) or by the
+// number of taps on the board (kPoolAvgExclude).
+hipError_t launchGraphPool(DevView in, float* out, int outStride, int kh, int kw, int dh, int dw, int mode, int boards,
+                           hipStream_t stream);
 
 // Channel concat (also a plain copy of one view): up to kMaxCopySegs views placed at channel dstOff[i]
 struct ConcatArgs {

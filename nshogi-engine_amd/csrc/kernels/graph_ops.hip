@@ -1,6 +1,7 @@
-// graph_ops.hip -- the general graph path's small kernels: the fused elementwise chain, the mean over the 81
-// squares, channel concat / copy, flatten to ONNX order, and the scatter into the evaluator's outputs.  One thread
+// graph_ops.hip -- the general graph path's small kernels: the fused elementwise chain, the mean and the max over
+// the 81 squares, channel concat / copy, flatten to ONNX order, and the scatter into the evaluator's outputs.  One thread
 // per output element; every kernel writes zeros into the channels between C and the row stride.
+#include "graph_act.h"
 #include "graph_kernels.h"
 
 namespace nsg {
@@ -9,19 +10,6 @@ namespace graph {
 namespace {
 
 constexpr int kThreads = 256;
-
-__device__ inline float applyAct(float v, int act) {
-    switch (act) {
-    case kActRelu: return v > 0.f ? v : 0.f;
-    case kActSigmoid: return 1.f / (1.f + expf(-v));
-    case kActTanh: return tanhf(v);
-    case kActSwish: return v / (1.f + expf(-v));
-    case kActSoftplus: return v > 20.f ? v : log1pf(expf(v));
-    case kActErf: return erff(v);
-    case kActGelu: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); // exact GELU
-    default: return v;
-    }
-}
 
 unsigned blocksFor(long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
@@ -56,6 +44,11 @@ __global__ __launch_bounds__(kThreads) void graphElt(EltArgs a) {
         case kEltAdd: v = r[x] + r[y]; break;
         case kEltSub: v = r[x] - r[y]; break;
         case kEltMul: v = r[x] * r[y]; break;
+        case kEltMax: v = fmaxf(r[x], r[y]); break;
+        case kEltMin: v = fminf(r[x], r[y]); break;
+        case kEltLeaky: v = r[x] > 0.f ? r[x] : r[x] * r[y]; break;
+        case kEltNeg: v = -r[x]; break;
+        case kEltAbs: v = fabsf(r[x]); break;
         default: v = r[x] / r[y]; break;
         }
         r[dst] = v;
@@ -74,6 +67,22 @@ __global__ __launch_bounds__(kThreads) void graphMean(const float* __restrict__ 
         const float* p = in + (size_t)b * 81 * inStride + inOff + c;
         for (int sq = 0; sq < 81; ++sq) s += p[(size_t)sq * inStride];
         s /= 81.f;
+    }
+    out[idx] = s;
+}
+
+// The max over the 81 squares; graphMean's indexing, so that graphMean itself stays as it was.
+__global__ __launch_bounds__(kThreads) void graphMax(const float* __restrict__ in, int inStride, int inOff, int C,
+                                                     float* __restrict__ out, int outStride, int boards) {
+    const long idx = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= (long)boards * outStride) return;
+    const long b = idx / outStride;
+    const int c = (int)(idx - b * outStride);
+    float s = 0.f;
+    if (c < C) {
+        const float* p = in + (size_t)b * 81 * inStride + inOff + c;
+        s = p[0];
+        for (int sq = 1; sq < 81; ++sq) s = fmaxf(s, p[(size_t)sq * inStride]);
     }
     out[idx] = s;
 }
@@ -135,6 +144,13 @@ hipError_t launchGraphElt(const EltArgs& a, hipStream_t stream) {
 hipError_t launchGraphMean(DevView in, float* out, int outStride, int boards, hipStream_t stream) {
     if (boards <= 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(graphMean, dim3(blocksFor((long)boards * outStride)), dim3(kThreads), 0, stream, in.p, in.stride,
+                       in.offset, in.C, out, outStride, boards);
+    return hipGetLastError();
+}
+
+hipError_t launchGraphMax(DevView in, float* out, int outStride, int boards, hipStream_t stream) {
+    if (boards <= 0 || in.offset + in.C > in.stride || outStride < in.C) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(graphMax, dim3(blocksFor((long)boards * outStride)), dim3(kThreads), 0, stream, in.p, in.stride,
                        in.offset, in.C, out, outStride, boards);
     return hipGetLastError();
 }

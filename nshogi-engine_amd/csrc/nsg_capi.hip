@@ -930,6 +930,12 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
         case gr::kLaunchMean:
             NSG_HIP(gr::launchGraphMean(dv(L.in), ptr(L.out), L.out.stride, B, s));
             break;
+        case gr::kLaunchMax:
+            NSG_HIP(gr::launchGraphMax(dv(L.in), ptr(L.out), L.out.stride, B, s));
+            break;
+        case gr::kLaunchPool:
+            NSG_HIP(gr::launchGraphPool(dv(L.in), ptr(L.out), L.out.stride, L.kh, L.kw, L.dh, L.dw, L.poolMode, B, s));
+            break;
         case gr::kLaunchConcat: {
             gr::ConcatArgs a{};
             for (size_t i = 0; i < L.segs.size(); ++i) {

@@ -97,6 +97,7 @@ class Planner {
     std::set<std::string> Outputs;
     std::vector<bool> Skip;          // nodes absorbed into an earlier launch
     std::vector<Node> Nodes;         // after the swish rewrite
+    std::map<std::string, size_t> ProducerOf; // tensor -> the live node that computes it
     std::vector<Group> Groups;
     std::vector<int> VirtStride;     // per produced tensor (virtual buffer)
     std::vector<bool> VirtSpatial;
@@ -221,6 +222,10 @@ class Planner {
         return Out;
     }
 
+    bool scalarAhead(const std::string& T, double* V, int Depth = 0) const;
+    int nodeAct(const Node& N) const;
+    void pool(const Node& N);
+    void split(const Node& N);
     void hostFold(const Node& N);
     void linear(const Node& N, size_t Index);
     void elementwise(const Node& N);
@@ -270,12 +275,19 @@ int actOf(const std::string& Op) {
     return kActNone;
 }
 bool isBinary(const std::string& Op) { return Op == "Add" || Op == "Sub" || Op == "Mul" || Op == "Div"; }
+// the other ops of the elementwise program: the clamp family, Max / Min of two operands, Abs, Neg
+bool isEltExtra(const std::string& Op) {
+    return Op == "Max" || Op == "Min" || Op == "Clip" || Op == "HardSwish" || Op == "HardSigmoid" || Op == "LeakyRelu" ||
+           Op == "PRelu" || Op == "Abs" || Op == "Neg";
+}
 
 const std::set<std::string>& opSet() {
     static const std::set<std::string> S = {
         "Conv", "BatchNormalization", "Relu", "Sigmoid", "Tanh", "Softplus", "Add", "Sub", "Mul", "Div",
         "GlobalAveragePool", "ReduceMean", "Flatten", "Reshape", "Squeeze", "Unsqueeze", "Gemm", "MatMul",
         "Concat", "Slice", "Identity", "Constant", "Transpose", "LayerNormalization", "Erf", "Softmax",
+        "MaxPool", "AveragePool", "GlobalMaxPool", "ReduceMax", "Split", "Clip", "HardSwish", "HardSigmoid", "LeakyRelu",
+        "PRelu", "Max", "Min", "Abs", "Neg",
         // folded on the host only (shape chains): refused on a runtime tensor
         "Shape", "Gather", "Cast", "Pow", "Sqrt"};
     return S;
@@ -301,6 +313,42 @@ std::vector<int> variesAlong(const std::vector<int64_t>& D, size_t R) {
     for (size_t K = 0; K < D.size(); ++K)
         if (D[K] != 1) Ax.push_back((int)(K + R - D.size()));
     return Ax;
+}
+
+// A constant scalar that may not be folded yet: the exporter puts a Clip's bounds behind Cast nodes that follow the
+// conv whose epilogue looks ahead at the Clip.
+bool Planner::scalarAhead(const std::string& T, double* V, int Depth) const {
+    auto It = Vals.find(T);
+    if (It != Vals.end()) {
+        const Val& C = It->second;
+        if (C.runtime || C.count() != 1 || (C.isInt && C.i[0] == kBatch)) return false;
+        *V = C.at(0);
+        return true;
+    }
+    auto Pr = ProducerOf.find(T);
+    if (Pr == ProducerOf.end() || Depth > 4) return false;
+    const Node& N = Nodes[Pr->second];
+    const bool FloatCast = N.Op == "Cast" && (N.attrI("to", 1) == 1 || N.attrI("to", 1) == 11);
+    if ((!FloatCast && N.Op != "Identity") || N.In.size() != 1) return false;
+    return scalarAhead(N.In[0], V, Depth + 1);
+}
+
+// The parameter-free activation a node is (a conv epilogue or one kEltAct instruction), or kActNone: relu6 is a Clip
+// with bounds exactly 0 and 6, the hard sigmoid is taken at alpha = 1/6 (within one f32 ulp) and beta = 0.5 only.
+int Planner::nodeAct(const Node& N) const {
+    if (isAct(N.Op)) return actOf(N.Op);
+    if (N.Op == "HardSwish") return kActHardSwish;
+    if (N.Op == "HardSigmoid") {
+        const float A = (float)N.attrF("alpha", 0.2), B = (float)N.attrF("beta", 0.5), K = 1.f / 6.f;
+        return B == 0.5f && (A == K || A == std::nextafterf(K, 0.f) || A == std::nextafterf(K, 1.f)) ? kActHardSigmoid : kActNone;
+    }
+    if (N.Op == "Clip") {
+        double Lo = 0, Hi = 0;
+        if (N.In.size() == 3 && !N.In[1].empty() && !N.In[2].empty() && scalarAhead(N.In[1], &Lo) && scalarAhead(N.In[2], &Hi) &&
+            Lo == 0.0 && Hi == 6.0)
+            return kActRelu6;
+    }
+    return kActNone;
 }
 
 // ---- host folding (constants and shape chains) ---------------------------------------------------------------
@@ -618,8 +666,8 @@ void Planner::linear(const Node& N, size_t Index) {
                 if (!Res.empty() || Act != kActNone || O.flatOfSpatial || O.dims != Dims || O.form != OutForm) break;
                 Res = Other;
             }
-        } else if (isAct(C->Op) && Act == kActNone && C->In[0] == Cur) {
-            Act = actOf(C->Op);
+        } else if (Act == kActNone && !C->In.empty() && C->In[0] == Cur && nodeAct(*C) != kActNone) {
+            Act = nodeAct(*C);
         } else {
             break;
         }
@@ -686,10 +734,25 @@ void Planner::linear(const Node& N, size_t Index) {
 void Planner::elementwise(const Node& N) {
     std::vector<std::vector<int64_t>> InDims;
     std::vector<int64_t> D;
-    const size_t Arity = isBinary(N.Op) ? 2 : 1;
+    const std::string& Op = N.Op;
+    const bool MinMax = Op == "Max" || Op == "Min";
+    if (MinMax && N.In.size() != 2) fail(N, Op + " of " + std::to_string(N.In.size()) + " operands: two only");
+    const int ActCode = nodeAct(N);
+    const size_t Arity = isBinary(Op) || MinMax || Op == "PRelu" ? 2 : 1;
+    if (Op == "PRelu") host(N, 1, "the slope");
+    // what the node adds to the program behind its operands, beyond one instruction and one register
+    const bool ClipLo = Op == "Clip" && (has(N, 1) || N.Attrs.count("min")), ClipHi = Op == "Clip" && (has(N, 2) || N.Attrs.count("max"));
+    int XSrcs = 0, XCode = 0, XRegs = 0;
+    if (ActCode == kActNone) {
+        if (Op == "Clip") XSrcs = ClipLo + ClipHi, XCode = XRegs = 2 * XSrcs;
+        else if (Op == "HardSigmoid") XSrcs = 4, XCode = XRegs = 8;
+        else if (Op == "LeakyRelu" || Op == "PRelu") XSrcs = 1, XCode = XRegs = 2;
+    }
     for (size_t K = 0; K < Arity; ++K) {
         const Val& V = get(N, K);
         std::vector<int64_t> Di = V.runtime && V.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)V.v.C * 81} : V.dims;
+        // a PRelu slope [C] on [N,C,9,9] is read per channel, like [C,1,1]
+        if (Op == "PRelu" && K == 1 && Di.size() == 1 && D.size() == 4 && Di[0] == D[1] && Di[0] != D[3]) Di = {Di[0], 1, 1};
         std::vector<int64_t> Bd;
         if (K == 0) D = Di;
         else if (!broadcast(D, Di, &Bd)) fail(N, "shapes " + dimsStr(D) + " and " + dimsStr(Di) + " do not broadcast");
@@ -754,8 +817,8 @@ void Planner::elementwise(const Node& N) {
                             (Open->spatial == NG.spatial || (Board && !Open->spatial));
         if (Domain && absorbable(Name)) {
             Group& Gr = Groups[(size_t)V.group];
-            if (NG.srcs.size() + Gr.srcs.size() <= (size_t)kMaxEltSrcs && NG.code.size() + Gr.code.size() + 2 <= (size_t)kMaxEltCode &&
-                NG.nregs + Gr.nregs + 1 <= kMaxEltRegs) {
+            if (NG.srcs.size() + Gr.srcs.size() + XSrcs <= (size_t)kMaxEltSrcs &&
+                NG.code.size() + Gr.code.size() + 2 + XCode <= (size_t)kMaxEltCode && NG.nregs + Gr.nregs + 1 + XRegs <= kMaxEltRegs) {
                 const int RB = NG.nregs, SB = (int)NG.srcs.size();
                 for (EltSrc S : Gr.srcs) {
                     if (Board && S.mode == kSrcSame) S.mode = kSrcBoard;
@@ -787,16 +850,49 @@ void Planner::elementwise(const Node& N) {
         NG.code.push_back(EltInstr{kEltLoad, (uint8_t)R, (uint8_t)(NG.srcs.size() - 1), 0});
         return R;
     };
+    auto scalarReg = [&](double Value) -> int {
+        if (NG.srcs.size() >= (size_t)kMaxEltSrcs) fail(N, "too many inputs for one fused launch");
+        EltSrc S;
+        S.mode = kSrcScalar;
+        S.scalar = (float)Value;
+        NG.srcs.push_back(S);
+        const int R = NG.nregs++;
+        NG.code.push_back(EltInstr{kEltLoad, (uint8_t)R, (uint8_t)(NG.srcs.size() - 1), 0});
+        return R;
+    };
+    auto instr = [&](int Code, int A, int B) -> int {
+        const int R = NG.nregs++;
+        NG.code.push_back(EltInstr{(uint8_t)Code, (uint8_t)R, (uint8_t)A, (uint8_t)B});
+        return R;
+    };
+    auto bound = [&](size_t Idx, const char* Attr, const char* What) -> double {
+        if (!has(N, Idx)) return N.attrF(Attr, 0.0);
+        const Val& B = host(N, Idx, What);
+        if (B.count() != 1 || (B.isInt && B.i[0] == kBatch)) fail(N, std::string(What) + " must be a scalar constant");
+        return B.at(0);
+    };
     int Out;
-    if (isAct(N.Op)) {
-        const int A = operand(0);
-        Out = NG.nregs++;
-        NG.code.push_back(EltInstr{kEltAct, (uint8_t)Out, (uint8_t)A, (uint8_t)actOf(N.Op)});
-    } else if (isBinary(N.Op)) {
+    if (ActCode != kActNone) {
+        Out = instr(kEltAct, operand(0), ActCode);
+    } else if (isBinary(Op) || MinMax) {
         const int A = operand(0), B = operand(1);
-        Out = NG.nregs++;
-        const int Op = N.Op == "Add" ? kEltAdd : N.Op == "Sub" ? kEltSub : N.Op == "Mul" ? kEltMul : kEltDiv;
-        NG.code.push_back(EltInstr{(uint8_t)Op, (uint8_t)Out, (uint8_t)A, (uint8_t)B});
+        Out = instr(Op == "Add" ? kEltAdd : Op == "Sub" ? kEltSub : Op == "Mul" ? kEltMul : Op == "Div" ? kEltDiv : Op == "Max" ? kEltMax : kEltMin, A, B);
+    } else if (Op == "Clip") { // min(max(x, lo), hi), either bound optional
+        Out = operand(0);
+        if (ClipLo) Out = instr(kEltMax, Out, scalarReg(bound(1, "min", "Clip's lower bound")));
+        if (ClipHi) Out = instr(kEltMin, Out, scalarReg(bound(2, "max", "Clip's upper bound")));
+    } else if (Op == "HardSigmoid") { // min(max(alpha x + beta, 0), 1) at any alpha and beta
+        Out = instr(kEltMul, operand(0), scalarReg(N.attrF("alpha", 0.2)));
+        Out = instr(kEltAdd, Out, scalarReg(N.attrF("beta", 0.5)));
+        Out = instr(kEltMax, Out, scalarReg(0.0));
+        Out = instr(kEltMin, Out, scalarReg(1.0));
+    } else if (Op == "LeakyRelu") {
+        Out = instr(kEltLeaky, operand(0), scalarReg(N.attrF("alpha", 0.01)));
+    } else if (Op == "PRelu") { // the slope: a scalar or per-channel constant, loaded like any constant operand
+        const int A = operand(0), B = operand(1);
+        Out = instr(kEltLeaky, A, B);
+    } else if (Op == "Abs" || Op == "Neg") {
+        Out = instr(Op == "Abs" ? kEltAbs : kEltNeg, operand(0), 0);
     } else { // BatchNormalization on a runtime tensor: y = x * s + t per channel
         if (N.In.size() < 5) fail(N, "expected scale, bias, mean and variance");
         const double Eps = N.attrF("epsilon", 1e-5);
@@ -1196,6 +1292,105 @@ void Planner::rewriteGelu() {
     }
 }
 
+// ---- MaxPool / AveragePool that keep the board: one kLaunchPool.  A MaxPool whose window is the whole board (what the
+// exporter writes for adaptive_max_pool2d(x, 1)) is the global max: one kLaunchMax.
+void Planner::pool(const Node& N) {
+    const Val& X = get(N, 0);
+    const bool Max = N.Op == "MaxPool";
+    if (X.form != kFormPlain || X.flatOfSpatial || !isSpatialDims(X.dims))
+        fail(N, "input " + dimsStr(X.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)X.v.C * 81} : X.dims) +
+                    " is not [N,C,9,9]: pooling runs on a spatial tensor only");
+    const int C = (int)X.dims[1];
+    const std::vector<int64_t> Ks = N.attrInts("kernel_shape", {});
+    if (Ks.size() != 2) fail(N, "a kernel_shape of two sizes expected");
+    const std::string KStr = std::to_string(Ks[0]) + "x" + std::to_string(Ks[1]);
+    if (N.Out.size() > 1 && !N.Out[1].empty() && Uses.count(N.Out[1]))
+        fail(N, "the Indices output '" + N.Out[1] + "' is used: only the pooled values are computed");
+    const std::vector<int64_t> Dil = N.attrInts("dilations", {1, 1});
+    if (Dil.size() != 2 || Dil[0] < 1 || Dil[1] < 1) fail(N, "two dilations of at least 1 expected");
+    const std::vector<int64_t> Pads = N.attrInts("pads", {0, 0, 0, 0});
+    const bool Ceil = N.attrI("ceil_mode", 0) != 0, AutoPad = N.Attrs.count("auto_pad") != 0;
+    Launch L;
+    L.name = N.Name;
+    if (Max && Ks == std::vector<int64_t>{9, 9} && Pads == std::vector<int64_t>{0, 0, 0, 0} && Dil == std::vector<int64_t>{1, 1} &&
+        !Ceil && !AutoPad) { // one window: the strides do not matter
+        L.kind = kLaunchMax;
+        L.in = ready(N.In[0]).v;
+        L.out = freshView(C, false);
+        Val V = runtimeVal(N, {kBatch, C, 1, 1});
+        V.v = L.out;
+        emit(L);
+        Vals[N.Out[0]] = V;
+        return;
+    }
+    for (int64_t S : N.attrInts("strides", {1, 1}))
+        if (S != 1) fail(N, "stride " + std::to_string(S) + ": only stride 1 (the output stays 9x9)");
+    if (Ks[0] < 1 || Ks[1] < 1 || Ks[0] > 9 || Ks[1] > 9 || Ks[0] % 2 == 0 || Ks[1] % 2 == 0)
+        fail(N, "a " + KStr + " kernel: only odd kernel sizes from 1 to 9 each way");
+    if (Ceil) fail(N, "ceil_mode 1: only ceil_mode 0");
+    if (!Max && Dil != std::vector<int64_t>{1, 1}) fail(N, "a dilated AveragePool: dilations on MaxPool only");
+    const int KH = (int)Ks[0], KW = (int)Ks[1];
+    const int DH = KH == 1 ? 1 : (int)std::min<int64_t>(Dil[0], 64), DW = KW == 1 ? 1 : (int)std::min<int64_t>(Dil[1], 64);
+    const int Hy = DH * (KH - 1) / 2, Hx = DW * (KW - 1) / 2;
+    if (Hy > kMaxConvHalo || Hx > kMaxConvHalo)
+        fail(N, "a " + KStr + " kernel at dilation " + std::to_string(Dil[0]) + "x" + std::to_string(Dil[1]) + " reaches " +
+                    std::to_string(std::max(Hy, Hx)) + " squares past the edge: the halo is at most " + std::to_string(kMaxConvHalo));
+    if (AutoPad) fail(N, "auto_pad: only explicit pads");
+    if (Pads != std::vector<int64_t>{Hy, Hx, Hy, Hx}) {
+        std::string Ps;
+        for (int64_t P1 : Pads) Ps += (Ps.empty() ? "" : ",") + std::to_string(P1);
+        fail(N, "pads [" + Ps + "] do not keep the 9x9 board: a " + KStr + " kernel at dilation " + std::to_string(DH) + "x" +
+                    std::to_string(DW) + " needs [" + std::to_string(Hy) + "," + std::to_string(Hx) + "," + std::to_string(Hy) + "," + std::to_string(Hx) + "]");
+    }
+    L.kind = kLaunchPool;
+    L.kh = KH;
+    L.kw = KW;
+    L.dh = DH;
+    L.dw = DW;
+    L.poolMode = Max ? kPoolMax : N.attrI("count_include_pad", 0) != 0 ? kPoolAvgInclude : kPoolAvgExclude;
+    L.in = ready(N.In[0]).v; // a view at any channel offset: the kernel reads an unaligned one with scalar loads
+    L.out = freshView(C, true);
+    Val V = runtimeVal(N, X.dims);
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+}
+
+// ---- Split along the channels: every output is a view, like Slice
+void Planner::split(const Node& N) {
+    const Val& X = get(N, 0);
+    if (X.flatOfSpatial) fail(N, "Split of a flattened [N,C*81] view of a spatial tensor");
+    const Val Src = ready(N.In[0]);
+    const int64_t Rank = (int64_t)Src.dims.size(), ChanAxis = Src.form == kFormToken ? 2 : 1;
+    int64_t Axis = N.attrI("axis", 0);
+    if (Axis < 0) Axis += Rank;
+    if (Axis != ChanAxis || Rank < 2) fail(N, "Split of " + dimsStr(Src.dims) + " along axis " + std::to_string(N.attrI("axis", 0)) + ": along the channels only");
+    const int64_t C = Src.v.C;
+    std::vector<int64_t> Sizes = has(N, 1) ? ints(N, 1, "the split sizes") : N.attrInts("split", {});
+    if (Sizes.empty()) {
+        const int64_t Parts = (int64_t)N.Out.size();
+        if (C % Parts) fail(N, std::to_string(C) + " channels do not split into " + std::to_string(Parts) + " equal parts");
+        Sizes.assign((size_t)Parts, C / Parts);
+    }
+    int64_t Sum = 0;
+    for (int64_t S : Sizes) {
+        if (S <= 0) fail(N, "an empty part");
+        Sum += S;
+    }
+    if (Sizes.size() != N.Out.size() || Sum != C)
+        fail(N, "the split sizes do not cover the " + std::to_string(C) + " channels with one part per output");
+    int64_t Off = 0;
+    for (size_t J = 0; J < Sizes.size(); Off += Sizes[J], ++J) {
+        if (N.Out[J].empty()) continue;
+        Val V = Src;
+        V.producer = N.Name;
+        V.v.offset += (int)Off;
+        V.v.C = (int)Sizes[J];
+        V.dims[(size_t)ChanAxis] = Sizes[J];
+        Vals[N.Out[J]] = V;
+    }
+}
+
 // ---- the plan ----------------------------------------------------------------------------------------------------
 void Planner::run() {
     // tensor contract (trt.cc:144-227)
@@ -1251,6 +1446,9 @@ void Planner::run() {
             }
     }
     for (const std::string& O : G.Outputs) ++Uses[O];
+    for (size_t K = 0; K < Nodes.size(); ++K)
+        if (!Skip[K])
+            for (const std::string& O : Nodes[K].Out) ProducerOf[O] = K;
 
     // constants
     for (const auto& KV : G.Inits) {
@@ -1329,26 +1527,31 @@ void Planner::run() {
             layerNorm(N);
         } else if (Op == "Conv" || Op == "Gemm" || Op == "MatMul") {
             linear(N, K);
-        } else if (isAct(Op) || isBinary(Op) || Op == "BatchNormalization") {
+        } else if (isAct(Op) || isBinary(Op) || isEltExtra(Op) || Op == "BatchNormalization") {
             if (Op == "BatchNormalization" && !X.runtime) fail(N, "expected a runtime input");
             if (isBinary(Op) && !get(N, 0).runtime && !get(N, 1).runtime) fail(N, "constant operands only");
             elementwise(N);
-        } else if (Op == "GlobalAveragePool" || Op == "ReduceMean") {
-            const bool Tok = X.form == kFormToken && Op == "ReduceMean";
+        } else if (Op == "MaxPool" || Op == "AveragePool") {
+            pool(N);
+        } else if (Op == "Split") {
+            split(N);
+        } else if (Op == "GlobalAveragePool" || Op == "ReduceMean" || Op == "GlobalMaxPool" || Op == "ReduceMax") {
+            const bool Reduce = Op == "ReduceMean" || Op == "ReduceMax";
+            const bool Tok = X.form == kFormToken && Reduce;
             if (!Tok && (X.flatOfSpatial || !isSpatialDims(X.dims))) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
             bool Keep = true;
-            if (Op == "ReduceMean") {
+            if (Reduce) {
                 std::vector<int64_t> Axes = has(N, 1) ? ints(N, 1, "axes") : N.attrInts("axes", {});
                 for (int64_t& A : Axes) if (A < 0) A += Tok ? 3 : 4;
                 std::sort(Axes.begin(), Axes.end());
                 if (Tok ? Axes != std::vector<int64_t>{1} : Axes != std::vector<int64_t>{2, 3})
-                    fail(N, "ReduceMean over the squares only: axes {2,3} of [N,C,9,9], axis 1 of a token tensor");
+                    fail(N, Op + " over the squares only: axes {2,3} of [N,C,9,9], axis 1 of a token tensor");
                 Keep = N.attrI("keepdims", 1) != 0;
-                if (Tok && Keep) fail(N, "ReduceMean of a token tensor with keepdims = 0 only");
+                if (Tok && Keep) fail(N, Op + " of a token tensor with keepdims = 0 only");
             }
             const int C = Tok ? (int)X.dims[2] : (int)X.dims[1];
             Launch L;
-            L.kind = kLaunchMean;
+            L.kind = Op == "GlobalMaxPool" || Op == "ReduceMax" ? kLaunchMax : kLaunchMean;
             L.name = N.Name;
             L.in = ready(N.In[0]).v;
             L.out = freshView(C, false);
@@ -1356,7 +1559,7 @@ void Planner::run() {
             V.v = L.out;
             emit(L);
             Vals[N.Out[0]] = V;
-        } else if (X.form == kFormToken && Op != "Slice" && Op != "Identity") {
+        } else if (X.form == kFormToken && Op != "Slice" && Op != "Identity") { // (Split on tokens is taken above)
             fail(N, "op '" + Op + "' is not supported on a token tensor " + dimsStr(X.dims));
         } else if (Op == "Flatten" || Op == "Reshape" || Op == "Squeeze" || Op == "Unsqueeze" || Op == "Identity") {
             // an open elementwise group read only here stays open: the reshaped tensor is its new result

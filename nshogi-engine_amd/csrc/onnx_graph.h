@@ -8,7 +8,7 @@
 //                                  81 squares is the spatial layout, so flatten(2).transpose(1,2) costs no launch
 //   flat [N,C] / [N,C,1,1] / [N] -> [row = board][stride] floats
 // stride = C rounded up to 16 (the conv kernel's K chunk); channels C..stride-1 are written as zero by every kernel.
-// A view names a buffer plus a channel offset, so `Slice` along the channel axis costs no launch.
+// A view names a buffer plus a channel offset, so `Slice` and `Split` along the channel axis cost no launch.
 #ifndef NSG_ONNX_GRAPH_H
 #define NSG_ONNX_GRAPH_H
 
@@ -28,7 +28,12 @@ constexpr int kMaxEltCode = 32; // instructions of one fused elementwise launch
 constexpr int kMaxEltRegs = 16;
 constexpr int kMaxCopySegs = 8; // sources of one channel concat
 
-enum Act { kActNone = 0, kActRelu, kActSigmoid, kActTanh, kActSwish, kActSoftplus, kActErf, kActGelu }; // kActGelu: exact (erf)
+// kActGelu: exact (erf); kActRelu6 = min(max(x, 0), 6); kActHardSigmoid = min(max(x / 6 + 0.5, 0), 1); kActHardSwish =
+// x * that.  All of them are parameter-free: a LeakyRelu, a PRelu, other Clip bounds are elementwise instructions.
+enum Act {
+    kActNone = 0, kActRelu, kActSigmoid, kActTanh, kActSwish, kActSoftplus, kActErf, kActGelu,
+    kActRelu6, kActHardSwish, kActHardSigmoid
+};
 
 // A runtime tensor as a launch sees it.  buf: -1 = the plane buffer (graph input), >= 0 = activation buffer.
 struct View {
@@ -40,9 +45,10 @@ struct View {
 };
 
 // Elementwise program: registers r0..r15; opcodes below.  LOAD reads source `a` into register `dst`.
-enum EltOp { kEltLoad = 0, kEltAct, kEltAdd, kEltSub, kEltMul, kEltDiv };
+// kEltLeaky: dst = a > 0 ? a : a * b (LeakyRelu: b holds alpha; PRelu: b holds the channel's slope); kEltNeg, kEltAbs: of a.
+enum EltOp { kEltLoad = 0, kEltAct, kEltAdd, kEltSub, kEltMul, kEltDiv, kEltMax, kEltMin, kEltLeaky, kEltNeg, kEltAbs };
 struct EltInstr {
-    uint8_t op, dst, a, b; // kEltAct: a = source register, b = Act; binary: dst = a (op) b
+    uint8_t op, dst, a, b; // kEltAct: a = source register, b = Act; binary: dst = a (op) b; unary: b unused
 };
 // How a source is read, relative to the element (row, c) of the output
 enum EltMode {
@@ -59,7 +65,12 @@ struct EltSrc {
     float scalar = 0.f;
 };
 
-enum LaunchKind { kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention };
+enum LaunchKind {
+    kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
+    kLaunchPool, kLaunchMax
+};
+// kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
+enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
 constexpr int kMaxHeadDim = 64; // channels per attention head (a multiple of 4)
 struct CopySeg { View v; int dstOff = 0; };
 
@@ -85,8 +96,11 @@ struct Launch {
     std::vector<EltSrc> srcs;
     std::vector<EltInstr> code;
     int eltOut = 0;  // the register stored
-    // kLaunchMean / kLaunchFlatten: `in`; kLaunchConcat: segments
+    // kLaunchMean / kLaunchMax / kLaunchFlatten: `in`; kLaunchConcat: segments
     std::vector<CopySeg> segs;
+    // kLaunchPool: `in` (a spatial view at any channel offset) -> out, kh x kw taps at dilations dh, dw under the conv's
+    // halo rule, stride 1: the board stays 9x9
+    int poolMode = kPoolMax;
     // kLaunchLayerNorm: over the channels of each row of `in` (token rows or boards); gamma at wOff, beta at biasOff
     float eps = 0.f;
     // kLaunchAttention: softmax(scale * q k^T + bias) v per (board, head) over the 81 squares.  q = `in`, k, v: token

@@ -87,6 +87,13 @@ inline float f32(Span S) {
     return V;
 }
 
+inline double f64(Span S) {
+    if (!S.p || S.n < 8) throw Error("malformed protobuf: a double field is not 8 bytes wide");
+    double V;
+    std::memcpy(&V, S.p, 8);
+    return V;
+}
+
 // a field that must be length-delimited (strings, sub-messages, raw_data)
 inline Span bytesOf(const Field& F, const char* What) {
     if (F.wire != 2) throw Error(std::string("malformed protobuf: ") + What + " is not length-delimited");
@@ -96,7 +103,7 @@ inline Span bytesOf(const Field& F, const char* What) {
 // ---- ONNX messages (onnx.proto3 field numbers) ----------------------------------------------
 struct Tensor {
     std::vector<int64_t> Dims;
-    std::vector<float> F;   // data_type FLOAT (1)
+    std::vector<float> F;   // data_type FLOAT (1); DOUBLE (11) is rounded to float on reading
     std::vector<int64_t> I; // data_type INT64 (7)
     bool IsFloat = true;
     size_t count() const { return IsFloat ? F.size() : I.size(); }
@@ -107,6 +114,7 @@ inline Tensor readTensor(Span S, std::string* Name) {
     int DataType = 0;
     Span Raw;
     bool HasRaw = false;
+    std::vector<double> Doubles;
     Reader R(S);
     Field Fd;
     while (R.next(&Fd)) {
@@ -126,6 +134,11 @@ inline Tensor readTensor(Span S, std::string* Name) {
             else { Reader P(Fd.bytes); while (!P.done()) T.I.push_back((int64_t)P.varint()); }
             break;
         case 8: if (Name) *Name = str(bytesOf(Fd, "a tensor name")); break;
+        case 10: // double_data
+            if (Fd.wire == 1) Doubles.push_back(f64(Fd.bytes));
+            else if (Fd.wire == 2) for (size_t K = 0; K + 8 <= Fd.bytes.n; K += 8) Doubles.push_back(f64(Span{Fd.bytes.p + K, 8}));
+            else throw Error("malformed protobuf: double_data is neither fixed64 nor packed");
+            break;
         case 9: Raw = bytesOf(Fd, "raw_data"); HasRaw = true; break;
         case 14: if (Fd.value != 0) throw Error("initializer with external data: not supported (keep the weights inside the .onnx file)"); break;
         default: break;
@@ -137,6 +150,13 @@ inline Tensor readTensor(Span S, std::string* Name) {
             T.F.resize(Raw.n / 4);
             std::memcpy(T.F.data(), Raw.p, T.F.size() * 4);
         }
+    } else if (DataType == 11) { // torch writes a Python float literal (clamp's bound) as a double constant behind a Cast
+        T.IsFloat = true;
+        if (HasRaw) {
+            Doubles.resize(Raw.n / 8);
+            std::memcpy(Doubles.data(), Raw.p, Doubles.size() * 8);
+        }
+        T.F.assign(Doubles.begin(), Doubles.end());
     } else if (DataType == 7) {
         T.IsFloat = false;
         if (HasRaw) {
@@ -145,7 +165,7 @@ inline Tensor readTensor(Span S, std::string* Name) {
         }
     } else {
         throw Error("initializer '" + (Name ? *Name : std::string()) + "': unsupported data type " +
-                    std::to_string(DataType) + " (float32 / int64 only)");
+                    std::to_string(DataType) + " (float32 / float64 / int64 only)");
     }
     size_t Want = 1;
     for (int64_t D : T.Dims) Want *= (size_t)D;

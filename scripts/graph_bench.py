@@ -6,6 +6,9 @@
     python scripts/graph_bench.py --attention [--out profiles/graph/attention_bench.json]   # the transformer row
     python scripts/graph_bench.py --trace-attention      # one shape of it for `rocprofv3 --kernel-trace --stats`
     python scripts/graph_bench.py --summarize-attention DIR/run_results.db   # each kernel's share of that forward
+    python scripts/graph_bench.py --pool [--out profiles/graph/pool_bench.json]   # the pooling row
+    python scripts/graph_bench.py --trace-pool      # it, a depthwise 3x3 and the family net for `rocprofv3 --kernel-trace`
+    python scripts/graph_bench.py --summarize-pool DIR/run_results.db   # graphPool against graphDepthwise and 8 TB/s
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
@@ -13,6 +16,11 @@ time with PyTorch's exporter; a geometry 20x256 net (tests/golden/make_onnx_geom
 stem, four blocks of two 5x5 convs, sixteen depthwise 7x7 + pointwise blocks), exported the same way.  evals/s =
 positions / wall time of `iters` computeBlocking calls after a warm-up.
 Also the SE net's load time (nsg_load on the .onnx file, planning and upload included).
+
+--pool: a pooling 20x256 net (tests/golden/make_onnx_pool_golden.py's PoolBenchNet: blocks that alternate the
+KataGo-style pooled bias and the inception-style 3x3 max / average pooling branch), exported at run time.  --trace-pool
+runs it at B = 512 beside a bare depthwise 3x3 of 256 channels (graphDepthwise: the yardstick of graphPool, same bytes,
+more work) and the forced family net (graphConv<9>, which must not move), all in one process.
 
 --attention: a pre-LN transformer over the 81 squares (tests/golden/make_onnx_attention_golden.py's PreNet with 8
 blocks, F = 256, H = 8 heads of d = 32, FFN width 1024), exported at run time, on the general path.
@@ -51,6 +59,21 @@ def geometry_onnx(path):
     mk.export_model(net, path)
 
 
+def pool_onnx(path):
+    import torch
+    import make_onnx_pool_golden as mk
+    torch.manual_seed(8)
+    net = mk.randomize(mk.PoolBenchNet(C=86, F=256, blocks=20), 16).eval()
+    mk.export_model(net, path)
+
+
+def depthwise3_onnx(path):
+    import torch
+    import make_onnx_geometry_golden as mk
+    torch.manual_seed(9)
+    mk.export_model(mk.randomize(mk.DwNet(256, 3, full=False), 17).eval(), path)
+
+
 def attention_onnx(path):
     import torch
     import make_onnx_attention_golden as mk
@@ -78,6 +101,7 @@ def rate(nsg, path, batch, prec="fp32", force=False, iters=50, warmup=5):
 
 TRACE_BATCH, TRACE_FORWARDS = 512, 23  # --trace: 3 warm-up + 20 timed forwards of the 20x256 net at B = 512 ...
 GEOM_FORWARDS = 8                      # ... then 3 + 5 of the geometry net
+POOL_FAMILY_FORWARDS = 8               # --trace-pool: 3 + 5 forwards of each of its three nets
 HBM_PEAK = 8.0e12  # bytes/s
 F32_MFMA_PEAK = 157.3e12  # FLOP/s at the 2.4 GHz peak clock (MI355X_MICROARCH): the run's clock is not sampled
 
@@ -129,6 +153,38 @@ def summarize(db):
               f"launches = {by / md / 1e12:.2f} TB/s = {by / md / HBM_PEAK:.3f} of {HBM_PEAK / 1e12:.0f} TB/s")
 
 
+def summarize_pool(db):
+    """graphPool (3x3, C = 256, B = 512; PoolBenchNet launches the max pool of a block before its average pool) as bytes
+    moved over time, beside graphDepthwise 3x3 at the same C and B and graphConv<9> of the forced family net, all from
+    one --trace-pool run."""
+    import sqlite3
+    import statistics
+    c = sqlite3.connect(db)
+    print(f"{'kernel':60s} {'calls':>6s} {'total ms':>10s} {'avg us':>9s}")
+    for n, k, t, a in c.execute("select name, count(*), sum(end-start), avg(end-start) from kernels group by name "
+                                "order by sum(end-start) desc"):
+        short = n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        print(f"{short:60s} {k:6d} {t / 1e6:10.2f} {a / 1e3:9.1f}")
+    by = 2.0 * TRACE_BATCH * 81 * 256 * 4  # one read and one write of the activation
+    print()
+    pl = [r[0] for r in c.execute("select end-start from kernels where name like '%graphPool%' order by start")]
+    dwt = [r[0] for r in c.execute("select end-start from kernels where name like '%graphDepthwise%' order by start")]
+    for label, d in (("graphPool 3x3 max", pl[0::2]), ("graphPool 3x3 avg (exclude pad)", pl[1::2]), ("graphDepthwise 3x3", dwt)):
+        if not d:
+            continue
+        m = statistics.median(d) * 1e-9
+        print(f"{label}, C=256, B={TRACE_BATCH}: {by / 1e6:.1f} MB per launch, median {m * 1e6:.1f} us (min {min(d) / 1e3:.1f}, max "
+              f"{max(d) / 1e3:.1f}) over {len(d)} launches = {by / m / 1e12:.2f} TB/s = {by / m / HBM_PEAK:.3f} of "
+              f"{HBM_PEAK / 1e12:.0f} TB/s")
+    d = [r[0] for r in c.execute("select end-start from kernels where name like '%graphConv<9>%' order by start")]
+    # the family net runs last: 41 launches per forward, the stem first
+    fam = d[-41 * POOL_FAMILY_FORWARDS:]
+    main_ns = [fam[i] for i in range(len(fam)) if i % 41 != 0]
+    if main_ns:
+        print(f"family net, 3x3 256->256 on graphConv<9>, B={TRACE_BATCH}: median {statistics.median(main_ns) / 1e3:.1f} us (min "
+              f"{min(main_ns) / 1e3:.1f}, max {max(main_ns) / 1e3:.1f}) over {len(main_ns)} launches")
+
+
 def summarize_attention(db):
     """Each kernel's share of the transformer's forward (a --trace-attention run), and the attention + LayerNorm time
     against the dense launches' (graphConv<1>)."""
@@ -159,7 +215,13 @@ def main():
     ap.add_argument("--attention", action="store_true", help="the 8-block F=256 H=8 transformer on the general path")
     ap.add_argument("--trace-attention", action="store_true", help="only that transformer at B=512, 13 forwards")
     ap.add_argument("--summarize-attention", metavar="DB", help="summarise the rocprofv3 database of a --trace-attention run")
+    ap.add_argument("--pool", action="store_true", help="the pooling 20x256 net on the general path")
+    ap.add_argument("--trace-pool", action="store_true", help="it, a depthwise 3x3 and the forced family net at B=512, 8 forwards each")
+    ap.add_argument("--summarize-pool", metavar="DB", help="summarise the rocprofv3 database of a --trace-pool run")
     a = ap.parse_args()
+    if a.summarize_pool:
+        summarize_pool(a.summarize_pool)
+        return
     if a.summarize:
         summarize(a.summarize)
         return
@@ -168,6 +230,28 @@ def main():
         return
     nsg = importlib.import_module("nshogi-engine_amd")
     tmp = tempfile.mkdtemp()
+    if a.pool or a.trace_pool:
+        pl = os.path.join(tmp, "pool_20x256.onnx")
+        pool_onnx(pl)
+        if a.trace_pool:
+            dw3, fam = os.path.join(tmp, "depthwise3_256.onnx"), os.path.join(tmp, "family_20x256.onnx")
+            depthwise3_onnx(dw3)
+            family_onnx(nsg, fam)
+            for label, path, force in (("pool", pl, False), ("depthwise3", dw3, False), ("family", fam, True)):
+                r, info = rate(nsg, path, TRACE_BATCH, force=force, iters=POOL_FAMILY_FORWARDS - 3, warmup=3)
+                print(json.dumps({label + "_trace_evals_per_s": r, "launches": info["launches"]}), flush=True)
+            return
+        row = {}
+        for b in [int(b) for b in a.batches.split(",")]:
+            r, info = rate(nsg, pl, b, iters=20 if b >= 256 else 50)
+            row[str(b)] = round(r, 1)
+            row.update(path=info["path"], launches=info["launches"], flops_per_position=info["flops_per_position"])
+        print("pool_20x256_general", json.dumps(row), flush=True)
+        out = a.out.replace("graph_bench.json", "pool_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump({"rows": {"pool_20x256_general": row}}, f, indent=1)
+        return
     if a.attention or a.trace_attention:
         att = os.path.join(tmp, "attention_8x256.onnx")
         attention_onnx(att)
