@@ -109,7 +109,10 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    that keeps the board, Split, and the clamp activations (relu6, hardswish,
  *    hardsigmoid, Clip, LeakyRelu, PRelu, Max, Min, Abs, Neg), whose stride-1 convs keep the 9x9 board with
  *    odd kernels up to 9x9 (1x9 and 9x1 too), dilations while a tap reaches
- *    at most 4 squares past the edge, group 1 or depthwise; and transformer or conv-plus-attention nets
+ *    at most 4 squares past the edge, group 1 or depthwise; the normalisations
+ *    without batch statistics (GroupNorm, InstanceNorm, a LayerNorm over the
+ *    channels between two Transposes, LayerNorm and RMSNorm written out in
+ *    elementary ops, as exported below opset 17); and transformer or conv-plus-attention nets
  *    over the 81 squares as tokens [N,81,C] -- dense layers, LayerNorm, exact
  *    GELU, a learned positional embedding and the multi-head attention
  *    pattern of section 13.3, which runs as one launch per block.  A general graph always runs in

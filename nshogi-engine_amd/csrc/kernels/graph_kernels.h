@@ -1,5 +1,5 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
-// graph_ops.hip, graph_attention.hip).
+// graph_ops.hip, graph_attention.hip, graph_norm.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -91,6 +91,19 @@ hipError_t launchGraphConcat(const ConcatArgs& a, hipStream_t stream);
 // biased variance, channels in.C..outStride-1 written as zero.  One wave per row.
 hipError_t launchGraphLayerNorm(DevView in, const float* gamma, const float* beta, float eps, float* out,
                                 int outStride, long rows, hipStream_t stream);
+
+// GroupNorm on spatial rows: group g is the C / groups consecutive channels from g C / groups (groups = C: instance norm;
+// groups = 1: one group), any group width.  Per (board, group) over its 81 C / groups elements: the mean, the biased
+// variance as the mean of squared deviations in a second pass, y = act((x - mean) / sqrt(var + eps) * gamma[c] + beta[c]),
+// act a parameter-free Act.  gamma, beta: [C].  `in` may start at any channel of its rows; out: rows of outStride = C
+// rounded up to 16, pad channels zero.  Every statistic is summed in an order fixed by (C, groups): see graph_norm.hip.
+hipError_t launchGraphGroupNorm(DevView in, int groups, const float* gamma, const float* beta, float eps, int act,
+                                float* out, int outStride, int boards, hipStream_t stream);
+
+// RMSNorm over the channels of each row (token rows or boards): y = x / sqrt(mean(x^2) + eps) * gamma[c], channels
+// in.C..outStride-1 written as zero.  One wave per row; `in` may start at any channel.
+hipError_t launchGraphRmsNorm(DevView in, const float* gamma, float eps, float* out, int outStride, long rows,
+                              hipStream_t stream);
 
 // Attention over the 81 squares, one workgroup per (board, head): out[:, h*d .. h*d+d-1] = softmax(scale * q_h k_h^T +
 // bias[h]) v_h.  q, k, v: token views of heads * headDim channels at offsets that are multiples of 4; headDim a

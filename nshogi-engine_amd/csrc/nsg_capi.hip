@@ -952,6 +952,13 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
         case gr::kLaunchLayerNorm:
             NSG_HIP(gr::launchGraphLayerNorm(dv(L.in), wts + L.wOff, wts + L.biasOff, L.eps, ptr(L.out), L.out.stride, rowsOf(L.out), s));
             break;
+        case gr::kLaunchGroupNorm:
+            NSG_HIP(gr::launchGraphGroupNorm(dv(L.in), L.groups, wts + L.wOff, wts + L.biasOff, L.eps, L.act, ptr(L.out),
+                                             L.out.stride, B, s));
+            break;
+        case gr::kLaunchRmsNorm:
+            NSG_HIP(gr::launchGraphRmsNorm(dv(L.in), wts + L.wOff, L.eps, ptr(L.out), L.out.stride, rowsOf(L.out), s));
+            break;
         case gr::kLaunchAttention:
             NSG_HIP(gr::launchGraphAttention(dv(L.in), dv(L.attK), dv(L.attV), L.hasBias ? wts + L.biasOff : nullptr, L.scale,
                                              ptr(L.out), L.out.stride, L.heads, L.headDim, B, s));

@@ -67,7 +67,7 @@ struct EltSrc {
 
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
-    kLaunchPool, kLaunchMax
+    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm
 };
 // kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
@@ -103,6 +103,10 @@ struct Launch {
     int poolMode = kPoolMax;
     // kLaunchLayerNorm: over the channels of each row of `in` (token rows or boards); gamma at wOff, beta at biasOff
     float eps = 0.f;
+    // kLaunchGroupNorm: `in` (a spatial view at any channel offset) normalised per (board, group of C / groups consecutive
+    // channels), then gamma at wOff, beta at biasOff (both [C], the pattern's constants folded in double) and `act`.
+    // kLaunchRmsNorm: x / sqrt(mean(x^2) + eps) * gamma over the channels of each row of `in`; gamma at wOff
+    int groups = 1;
     // kLaunchAttention: softmax(scale * q k^T + bias) v per (board, head) over the 81 squares.  q = `in`, k, v: token
     // views of heads * headDim channels; bias (hasBias): [heads][81][81] at biasOff; out: token rows, head h at
     // channels h * headDim

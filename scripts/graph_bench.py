@@ -9,6 +9,9 @@
     python scripts/graph_bench.py --pool [--out profiles/graph/pool_bench.json]   # the pooling row
     python scripts/graph_bench.py --trace-pool      # it, a depthwise 3x3 and the family net for `rocprofv3 --kernel-trace`
     python scripts/graph_bench.py --summarize-pool DIR/run_results.db   # graphPool against graphDepthwise and 8 TB/s
+    python scripts/graph_bench.py --norm [--out profiles/graph/norm_bench.json]   # the GroupNorm row
+    python scripts/graph_bench.py --trace-norm      # GroupNorm at three group counts, a max pool and a depthwise 3x3
+    python scripts/graph_bench.py --summarize-norm DIR/run_results.db [--out profiles/graph/norm_bench.json]
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
@@ -21,6 +24,12 @@ Also the SE net's load time (nsg_load on the .onnx file, planning and upload inc
 KataGo-style pooled bias and the inception-style 3x3 max / average pooling branch), exported at run time.  --trace-pool
 runs it at B = 512 beside a bare depthwise 3x3 of 256 channels (graphDepthwise: the yardstick of graphPool, same bytes,
 more work) and the forced family net (graphConv<9>, which must not move), all in one process.
+
+--norm: the 20x256 residual net with GroupNorm(32 groups)-ReLU in place of every BatchNorm-ReLU
+(tests/golden/make_onnx_norm_golden.py's NormBenchNet), exported at run time.  --trace-norm runs, in one process at
+B = 512 and C = 256, a bare GroupNorm of 32 groups, of 256 groups (instance norm) and of one group (graphGroupNorm), a
+3x3 max pool (graphPool) and a bare depthwise 3x3 (graphDepthwise): five kernels that each read and write the same
+84.9 MB.  --summarize-norm prints their medians and ranges and adds them to the --norm file.
 
 --attention: a pre-LN transformer over the 81 squares (tests/golden/make_onnx_attention_golden.py's PreNet with 8
 blocks, F = 256, H = 8 heads of d = 32, FFN width 1024), exported at run time, on the general path.
@@ -65,6 +74,28 @@ def pool_onnx(path):
     torch.manual_seed(8)
     net = mk.randomize(mk.PoolBenchNet(C=86, F=256, blocks=20), 16).eval()
     mk.export_model(net, path)
+
+
+def norm_onnx(path):
+    import torch
+    import make_onnx_norm_golden as mk
+    torch.manual_seed(10)
+    mk.export_model(mk.randomize(mk.NormBenchNet(C=86, F=256, blocks=20, G=32), 18).eval(), path)
+
+
+def groupnorm_onnx(path, groups):
+    """A 3x3 stem of 256 channels and one bare GroupNorm behind it."""
+    import torch
+    import make_onnx_norm_golden as mk
+    torch.manual_seed(11)
+    mk.export_model(mk.randomize(mk.NormNet(256, torch.nn.GroupNorm(groups, 256)), 19).eval(), path)
+
+
+def maxpool3_onnx(path):
+    import torch
+    import make_onnx_norm_golden as mk
+    torch.manual_seed(12)
+    mk.export_model(mk.randomize(mk.NormNet(256, torch.nn.MaxPool2d(3, 1, 1)), 20).eval(), path)
 
 
 def depthwise3_onnx(path):
@@ -185,6 +216,46 @@ def summarize_pool(db):
               f"{min(main_ns) / 1e3:.1f}, max {max(main_ns) / 1e3:.1f}) over {len(main_ns)} launches")
 
 
+NORM_TRACE = (("graphGroupNorm G=32", 32), ("graphGroupNorm G=256", 256), ("graphGroupNorm G=1", 1))
+
+
+def summarize_norm(db, out):
+    """graphGroupNorm at C = 256, B = 512 with 32, 256 and 1 groups (run in that order, POOL_FAMILY_FORWARDS launches
+    each) beside graphPool 3x3 max and graphDepthwise 3x3 from the same --trace-norm run: the same bytes each."""
+    import sqlite3
+    import statistics
+    c = sqlite3.connect(db)
+    print(f"{'kernel':60s} {'calls':>6s} {'total ms':>10s} {'avg us':>9s}")
+    for n, k, t, a in c.execute("select name, count(*), sum(end-start), avg(end-start) from kernels group by name "
+                                "order by sum(end-start) desc"):
+        short = n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        print(f"{short:60s} {k:6d} {t / 1e6:10.2f} {a / 1e3:9.1f}")
+    by = 2.0 * TRACE_BATCH * 81 * 256 * 4  # one read and one write of the activation
+    print()
+    gn = [r[0] for r in c.execute("select end-start from kernels where name like '%graphGroupNorm%' order by start")]
+    rows = [(label, gn[i * POOL_FAMILY_FORWARDS:(i + 1) * POOL_FAMILY_FORWARDS]) for i, (label, _) in enumerate(NORM_TRACE)]
+    rows.append(("graphPool 3x3 max", [r[0] for r in c.execute("select end-start from kernels where name like '%graphPool%' order by start")]))
+    rows.append(("graphDepthwise 3x3", [r[0] for r in c.execute("select end-start from kernels where name like '%graphDepthwise%' order by start")]))
+    res = {}
+    for label, d in rows:
+        if not d:
+            continue
+        m = statistics.median(d) * 1e-9
+        res[label] = {"median_us": round(m * 1e6, 1), "min_us": round(min(d) / 1e3, 1), "max_us": round(max(d) / 1e3, 1),
+                      "launches": len(d), "TB_per_s": round(by / m / 1e12, 2)}
+        print(f"{label}, C=256, B={TRACE_BATCH}: {by / 1e6:.1f} MB per launch, median {m * 1e6:.1f} us (min {min(d) / 1e3:.1f}, max "
+              f"{max(d) / 1e3:.1f}) over {len(d)} launches = {by / m / 1e12:.2f} TB/s = {by / m / HBM_PEAK:.3f} of "
+              f"{HBM_PEAK / 1e12:.0f} TB/s")
+    if out:
+        doc = {}
+        if os.path.exists(out):
+            with open(out) as f:
+                doc = json.load(f)
+        doc["trace_b512_c256"] = res
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
 def summarize_attention(db):
     """Each kernel's share of the transformer's forward (a --trace-attention run), and the attention + LayerNorm time
     against the dense launches' (graphConv<1>)."""
@@ -218,7 +289,13 @@ def main():
     ap.add_argument("--pool", action="store_true", help="the pooling 20x256 net on the general path")
     ap.add_argument("--trace-pool", action="store_true", help="it, a depthwise 3x3 and the forced family net at B=512, 8 forwards each")
     ap.add_argument("--summarize-pool", metavar="DB", help="summarise the rocprofv3 database of a --trace-pool run")
+    ap.add_argument("--norm", action="store_true", help="the 20x256 net with GroupNorm(32)-ReLU on the general path")
+    ap.add_argument("--trace-norm", action="store_true", help="GroupNorm of 32, 256 and 1 groups, a 3x3 max pool and a depthwise 3x3 at B=512, C=256")
+    ap.add_argument("--summarize-norm", metavar="DB", help="summarise the rocprofv3 database of a --trace-norm run")
     a = ap.parse_args()
+    if a.summarize_norm:
+        summarize_norm(a.summarize_norm, a.out.replace("graph_bench.json", "norm_bench.json"))
+        return
     if a.summarize_pool:
         summarize_pool(a.summarize_pool)
         return
@@ -230,6 +307,34 @@ def main():
         return
     nsg = importlib.import_module("nshogi-engine_amd")
     tmp = tempfile.mkdtemp()
+    if a.trace_norm:
+        jobs = [(label, (lambda p, g=g: groupnorm_onnx(p, g))) for label, g in NORM_TRACE]
+        jobs += [("graphPool 3x3 max", maxpool3_onnx), ("graphDepthwise 3x3", depthwise3_onnx)]
+        for i, (label, make) in enumerate(jobs):
+            path = os.path.join(tmp, f"norm_trace_{i}.onnx")
+            make(path)
+            r, info = rate(nsg, path, TRACE_BATCH, iters=POOL_FAMILY_FORWARDS - 3, warmup=3)
+            print(json.dumps({label: r, "launches": info["launches"]}), flush=True)
+        return
+    if a.norm:
+        nm = os.path.join(tmp, "norm_20x256.onnx")
+        norm_onnx(nm)
+        row = {}
+        for b in [int(b) for b in a.batches.split(",")]:
+            r, info = rate(nsg, nm, b, iters=20 if b >= 256 else 50)
+            row[str(b)] = round(r, 1)
+            row.update(path=info["path"], launches=info["launches"], flops_per_position=info["flops_per_position"])
+        print("groupnorm_20x256_general", json.dumps(row), flush=True)
+        out = a.out.replace("graph_bench.json", "norm_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        doc = {}
+        if os.path.exists(out):
+            with open(out) as f:
+                doc = json.load(f)
+        doc["rows"] = {"groupnorm_20x256_general": row}
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
+        return
     if a.pool or a.trace_pool:
         pl = os.path.join(tmp, "pool_20x256.onnx")
         pool_onnx(pl)
