@@ -18,10 +18,14 @@ __device__ inline float applyAct(float v, int act) {
     case kActSwish: return v / (1.f + expf(-v));
     case kActSoftplus: return v > 20.f ? v : log1pf(expf(v)); // torch's threshold
     case kActErf: return erff(v);
-    case kActGelu: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); // exact GELU
+    // exact GELU; 1 + erf(x) as erfc(-x), which keeps its relative accuracy where erf(x) is near -1 (1 + erff(x) is 0
+    // from x = -4 on, and a few bits above that)
+    case kActGelu: return 0.5f * v * erfcf(v * -0.70710678118654752f);
     case kActRelu6: return fminf(fmaxf(v, 0.f), 6.f);
-    case kActHardSwish: return v * fminf(fmaxf(v * (1.f / 6.f) + 0.5f, 0.f), 1.f);
-    case kActHardSigmoid: return fminf(fmaxf(v * (1.f / 6.f) + 0.5f, 0.f), 1.f);
+    // relu6(v + 3) / 6 as torch defines it: v + 3 is exact around the knee at -3, where v / 6 + 0.5 cancels and
+    // carries the rounding of v / 6 into the result (8 to 11 ulps on a grid of 1/8)
+    case kActHardSwish: return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);
+    case kActHardSigmoid: return fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);
     default: return v;
     }
 }

@@ -763,7 +763,9 @@ void Planner::elementwise(const Node& N) {
     if (ActCode == kActNone) {
         if (Op == "Clip") XSrcs = ClipLo + ClipHi, XCode = XRegs = 2 * XSrcs;
         else if (Op == "HardSigmoid") XSrcs = 4, XCode = XRegs = 8;
-        else if (Op == "LeakyRelu" || Op == "PRelu") XSrcs = 1, XCode = XRegs = 2;
+        else if (Op == "LeakyRelu") XSrcs = 1, XCode = XRegs = 2;
+        else if (Op == "PRelu") XCode = XRegs = 1; // LeakyRelu's budget; the slope's source and load count as an operand to come
+        else if (Op == "BatchNormalization") XSrcs = 2, XCode = XRegs = 3;
     }
     for (size_t K = 0; K < Arity; ++K) {
         const Val& V = get(N, K);
@@ -834,8 +836,13 @@ void Planner::elementwise(const Node& N) {
                             (Open->spatial == NG.spatial || (Board && !Open->spatial));
         if (Domain && absorbable(Name)) {
             Group& Gr = Groups[(size_t)V.group];
-            if (NG.srcs.size() + Gr.srcs.size() + XSrcs <= (size_t)kMaxEltSrcs &&
-                NG.code.size() + Gr.code.size() + 2 + XCode <= (size_t)kMaxEltCode && NG.nregs + Gr.nregs + 1 + XRegs <= kMaxEltRegs) {
+            // inline it only if the rest of the node still fits behind it: every operand still to come takes at least
+            // one source and one register (a constant, or a tensor read from memory), then the node's scalars and its
+            // own instruction.  Otherwise the group is launched and read as one source, which cuts the chain here.
+            const size_t Rest = Arity - 1 - K;
+            if (NG.srcs.size() + Gr.srcs.size() + Rest + XSrcs <= (size_t)kMaxEltSrcs &&
+                NG.code.size() + Gr.code.size() + 2 + XCode <= (size_t)kMaxEltCode &&
+                NG.nregs + Gr.nregs + (int)Rest + 1 + XRegs <= kMaxEltRegs) {
                 const int RB = NG.nregs, SB = (int)NG.srcs.size();
                 for (EltSrc S : Gr.srcs) {
                     if (Board && S.mode == kSrcSame) S.mode = kSrcBoard;
@@ -899,12 +906,14 @@ void Planner::elementwise(const Node& N) {
         if (ClipLo) Out = instr(kEltMax, Out, scalarReg(bound(1, "min", "Clip's lower bound")));
         if (ClipHi) Out = instr(kEltMin, Out, scalarReg(bound(2, "max", "Clip's upper bound")));
     } else if (Op == "HardSigmoid") { // min(max(alpha x + beta, 0), 1) at any alpha and beta
-        Out = instr(kEltMul, operand(0), scalarReg(N.attrF("alpha", 0.2)));
+        Out = operand(0); // before the scalars: the operand's budget counts them as still to come
+        Out = instr(kEltMul, Out, scalarReg(N.attrF("alpha", 0.2)));
         Out = instr(kEltAdd, Out, scalarReg(N.attrF("beta", 0.5)));
         Out = instr(kEltMax, Out, scalarReg(0.0));
         Out = instr(kEltMin, Out, scalarReg(1.0));
     } else if (Op == "LeakyRelu") {
-        Out = instr(kEltLeaky, operand(0), scalarReg(N.attrF("alpha", 0.01)));
+        Out = operand(0);
+        Out = instr(kEltLeaky, Out, scalarReg(N.attrF("alpha", 0.01)));
     } else if (Op == "PRelu") { // the slope: a scalar or per-channel constant, loaded like any constant operand
         const int A = operand(0), B = operand(1);
         Out = instr(kEltLeaky, A, B);
