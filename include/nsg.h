@@ -107,7 +107,10 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    is built only from its closed op set (section 13.2): convolutional nets
  *    with SE / global mean and max pooling, stride-1 max and average pooling
  *    that keeps the board, Split, and the clamp activations (relu6, hardswish,
- *    hardsigmoid, Clip, LeakyRelu, PRelu, Max, Min, Abs, Neg), whose stride-1 convs keep the 9x9 board with
+ *    hardsigmoid, Clip, LeakyRelu, PRelu, Max, Min, Abs, Neg), elementwise
+ *    maths on run-time tensors (Exp, Log, Sqrt, Reciprocal, Pow with a constant
+ *    scalar exponent) and Mish, tanh-GELU and softsign as the exporter writes
+ *    them (one fused activation each), whose stride-1 convs keep the 9x9 board with
  *    odd kernels up to 9x9 (1x9 and 9x1 too), dilations while a tap reaches
  *    at most 4 squares past the edge, group 1 or depthwise; the normalisations
  *    without batch statistics (GroupNorm, InstanceNorm, a LayerNorm over the

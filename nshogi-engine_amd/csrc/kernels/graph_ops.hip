@@ -49,6 +49,7 @@ __global__ __launch_bounds__(kThreads) void graphElt(EltArgs a) {
         case kEltLeaky: v = r[x] > 0.f ? r[x] : r[x] * r[y]; break;
         case kEltNeg: v = -r[x]; break;
         case kEltAbs: v = fabsf(r[x]); break;
+        case kEltPow: v = powf(r[x], r[y]); break;
         default: v = r[x] / r[y]; break;
         }
         r[dst] = v;

@@ -249,6 +249,8 @@ class Planner {
     bool formView(const Node& N);   // Transpose, and Reshape / Flatten to or from the forms above
     bool attentionOp(const Node& N); // MatMul / Mul / Div / Add / Softmax on the attention pattern's 4-D tensors
     void rewriteGelu();
+    void rewriteMath();
+    bool powExponent(const Node& N, double* E) const;
     std::vector<int64_t> reshapeTarget(const Node& N, const std::vector<int64_t>& SD);
     // the tensor feeds one node only: the attention pattern's interior tensors are never materialised
     // (a Shape node reads no data: torch emits one on q for `q.size(-1) ** -0.5`)
@@ -277,8 +279,10 @@ class Planner {
     size_t indexOf(const Node* N) const { return (size_t)(N - Nodes.data()); }
 };
 
+// (Swish, Gelu, MishAct, GeluTanh and Softsign are the planner's own nodes, written by its rewrites)
 bool isAct(const std::string& Op) {
-    return Op == "Relu" || Op == "Sigmoid" || Op == "Tanh" || Op == "Softplus" || Op == "Swish" || Op == "Erf" || Op == "Gelu";
+    return Op == "Relu" || Op == "Sigmoid" || Op == "Tanh" || Op == "Softplus" || Op == "Swish" || Op == "Erf" || Op == "Gelu" ||
+           Op == "Exp" || Op == "Log" || Op == "Sqrt" || Op == "Reciprocal" || Op == "MishAct" || Op == "GeluTanh" || Op == "Softsign";
 }
 int actOf(const std::string& Op) {
     if (Op == "Relu") return kActRelu;
@@ -288,6 +292,13 @@ int actOf(const std::string& Op) {
     if (Op == "Swish") return kActSwish;
     if (Op == "Erf") return kActErf;
     if (Op == "Gelu") return kActGelu;
+    if (Op == "Exp") return kActExp;
+    if (Op == "Log") return kActLog;
+    if (Op == "Sqrt") return kActSqrt;
+    if (Op == "Reciprocal") return kActRecip;
+    if (Op == "MishAct") return kActMish;
+    if (Op == "GeluTanh") return kActGeluTanh;
+    if (Op == "Softsign") return kActSoftsign;
     return kActNone;
 }
 bool isBinary(const std::string& Op) { return Op == "Add" || Op == "Sub" || Op == "Mul" || Op == "Div"; }
@@ -303,10 +314,9 @@ const std::set<std::string>& opSet() {
         "GlobalAveragePool", "ReduceMean", "Flatten", "Reshape", "Squeeze", "Unsqueeze", "Gemm", "MatMul",
         "Concat", "Slice", "Identity", "Constant", "Transpose", "LayerNormalization", "Erf", "Softmax",
         "MaxPool", "AveragePool", "GlobalMaxPool", "ReduceMax", "Split", "Clip", "HardSwish", "HardSigmoid", "LeakyRelu",
-        "PRelu", "Max", "Min", "Abs", "Neg", "InstanceNormalization",
+        "PRelu", "Max", "Min", "Abs", "Neg", "InstanceNormalization", "Exp", "Log", "Sqrt", "Reciprocal", "Pow",
         // folded on the host only (shape chains): refused on a runtime tensor
-        // (Pow and Sqrt also inside the decomposed LayerNorm / RMSNorm patterns)
-        "Shape", "Gather", "Cast", "Pow", "Sqrt"};
+        "Shape", "Gather", "Cast"};
     return S;
 }
 
@@ -350,10 +360,19 @@ bool Planner::scalarAhead(const std::string& T, double* V, int Depth) const {
     return scalarAhead(N.In[0], V, Depth + 1);
 }
 
+// A Pow's exponent when it is a constant scalar (folded already, or still behind the exporter's Cast).
+bool Planner::powExponent(const Node& N, double* E) const {
+    return N.In.size() == 2 && !N.In[1].empty() && scalarAhead(N.In[1], E);
+}
+
 // The parameter-free activation a node is (a conv epilogue or one kEltAct instruction), or kActNone: relu6 is a Clip
 // with bounds exactly 0 and 6, the hard sigmoid is taken at alpha = 1/6 (within one f32 ulp) and beta = 0.5 only.
 int Planner::nodeAct(const Node& N) const {
     if (isAct(N.Op)) return actOf(N.Op);
+    if (N.Op == "Pow") { // x ** 0.5 and x ** -1 are the square root and the reciprocal
+        double E = 0;
+        return powExponent(N, &E) && (E == 0.5 || E == -1.0) ? (E == 0.5 ? kActSqrt : kActRecip) : kActNone;
+    }
     if (N.Op == "HardSwish") return kActHardSwish;
     if (N.Op == "HardSigmoid") {
         const float A = (float)N.attrF("alpha", 0.2), B = (float)N.attrF("beta", 0.5), K = 1.f / 6.f;
@@ -534,13 +553,14 @@ void Planner::hostFold(const Node& N) {
         Out() = R;
         return;
     }
-    if (Op == "Sqrt" || Op == "Pow") { // torch emits them for `d ** -0.5` when d comes from size()
+    if (Op == "Sqrt" || Op == "Pow" || Op == "Exp" || Op == "Log" || Op == "Reciprocal") { // torch emits them for `d ** -0.5` when d comes from size()
         const Val* Y = Op == "Pow" ? &host(N, 1, "the exponent") : nullptr;
         if (Y && Y->count() != 1 && Y->count() != X.count()) fail(N, "constant folding supports equal shapes or a scalar exponent");
         R.dims = X.dims;
         for (size_t K = 0; K < X.count(); ++K) {
             if (X.isInt && X.i[K] == kBatch) fail(N, "arithmetic on the symbolic batch dimension");
-            R.f.push_back(Y ? std::pow(X.at(K), Y->at(Y->count() == 1 ? 0 : K)) : std::sqrt(X.at(K)));
+            const double A = X.at(K);
+            R.f.push_back(Y ? std::pow(A, Y->at(Y->count() == 1 ? 0 : K)) : Op == "Sqrt" ? std::sqrt(A) : Op == "Exp" ? std::exp(A) : Op == "Log" ? std::log(A) : 1.0 / A);
         }
         Out() = R;
         return;
@@ -757,6 +777,16 @@ void Planner::elementwise(const Node& N) {
     const int ActCode = nodeAct(N);
     const size_t Arity = isBinary(Op) || MinMax || Op == "PRelu" ? 2 : 1;
     if (Op == "PRelu") host(N, 1, "the slope");
+    // Pow(x, c) at a constant scalar c, decided here: 2, 3, 4 as products, -0.5 and -2 as a reciprocal behind the square
+    // root or the square (0.5 and -1 are activations, 1 never gets here), anything else powf with c as a scalar source
+    double PowE = 0;
+    if (Op == "Pow") {
+        const Val& E = get(N, 1);
+        if (E.runtime || E.count() != 1 || (E.isInt && E.i[0] == kBatch)) fail(N, "the exponent must be a constant scalar");
+        PowE = E.at(0);
+    }
+    const bool PowTwoStep = Op == "Pow" && (PowE == 3.0 || PowE == 4.0 || PowE == -0.5 || PowE == -2.0);
+    const bool PowGeneral = Op == "Pow" && ActCode == kActNone && PowE != 2.0 && !PowTwoStep;
     // what the node adds to the program behind its operands, beyond one instruction and one register
     const bool ClipLo = Op == "Clip" && (has(N, 1) || N.Attrs.count("min")), ClipHi = Op == "Clip" && (has(N, 2) || N.Attrs.count("max"));
     int XSrcs = 0, XCode = 0, XRegs = 0;
@@ -766,6 +796,8 @@ void Planner::elementwise(const Node& N) {
         else if (Op == "LeakyRelu") XSrcs = 1, XCode = XRegs = 2;
         else if (Op == "PRelu") XCode = XRegs = 1; // LeakyRelu's budget; the slope's source and load count as an operand to come
         else if (Op == "BatchNormalization") XSrcs = 2, XCode = XRegs = 3;
+        else if (PowTwoStep) XCode = XRegs = 1;
+        else if (PowGeneral) XSrcs = 1, XCode = XRegs = 1;
     }
     for (size_t K = 0; K < Arity; ++K) {
         const Val& V = get(N, K);
@@ -919,6 +951,25 @@ void Planner::elementwise(const Node& N) {
         Out = instr(kEltLeaky, A, B);
     } else if (Op == "Abs" || Op == "Neg") {
         Out = instr(Op == "Abs" ? kEltAbs : kEltNeg, operand(0), 0);
+    } else if (Op == "Pow") {
+        const int A = operand(0);
+        if (PowE == 2.0) {
+            Out = instr(kEltMul, A, A);
+        } else if (PowE == 3.0) {
+            const int Sq = instr(kEltMul, A, A);
+            Out = instr(kEltMul, Sq, A);
+        } else if (PowE == 4.0) {
+            const int Sq = instr(kEltMul, A, A);
+            Out = instr(kEltMul, Sq, Sq);
+        } else if (PowE == -0.5) {
+            const int Rt = instr(kEltAct, A, kActSqrt);
+            Out = instr(kEltAct, Rt, kActRecip);
+        } else if (PowE == -2.0) {
+            const int Sq = instr(kEltMul, A, A);
+            Out = instr(kEltAct, Sq, kActRecip);
+        } else {
+            Out = instr(kEltPow, A, scalarReg(PowE));
+        }
     } else { // BatchNormalization on a runtime tensor: y = x * s + t per channel
         if (N.In.size() < 5) fail(N, "expected scale, bias, mean and variance");
         const double Eps = N.attrF("epsilon", 1e-5);
@@ -1575,6 +1626,143 @@ void Planner::rewriteGelu() {
     }
 }
 
+// Mish, tanh-GELU and softsign as the exporter writes them become one node each (MishAct, GeluTanh, Softsign), then an
+// activation like any other.  x is the one tensor a pattern reads more than once; every other tensor inside has one
+// consumer and is no graph output; commutative nodes match in either operand order; the constants are compared as
+// f32 within one ulp.  A chain that starts like a pattern and then deviates is left as it is: plain elementwise nodes.
+//   Mish       Mul(x, Tanh(Softplus(x)))
+//   tanh-GELU  Mul(Mul(x, Add(Tanh(Mul(Add(x, Mul(x^3, 0.044715)), sqrt(2/pi))), 1)), 0.5), the 0.5 on either Mul;
+//              x^3 is Mul(Mul(x, x), x) or Pow(x, 3)
+//   softsign   Div(x, Add(Abs(x), 1))
+void Planner::rewriteMath() {
+    std::map<std::string, int> Cnt;
+    std::map<std::string, size_t> Producer;
+    for (size_t K = 0; K < Nodes.size(); ++K) {
+        if (Skip[K]) continue;
+        for (const std::string& I : Nodes[K].In) ++Cnt[I];
+        for (const std::string& O : Nodes[K].Out) Producer[O] = K;
+    }
+    auto near = [](double V, double Want) {
+        const float A = (float)V, B = (float)Want;
+        return A == B || A == std::nextafterf(B, 0.f) || A == std::nextafterf(B, 2.f * B);
+    };
+    auto scalar = [&](const std::string& T, double Want) {
+        auto It = G.Inits.find(T);
+        return It != G.Inits.end() && It->second.IsFloat && It->second.F.size() == 1 && near(It->second.F[0], Want);
+    };
+    // the node producing the interior tensor T when it has op `OpName`, or -1
+    auto inner = [&](const std::string& T, const char* OpName, size_t Arity) -> int {
+        auto It = Producer.find(T);
+        if (It == Producer.end() || Skip[It->second] || Nodes[It->second].Op != OpName || Nodes[It->second].In.size() != Arity ||
+            Cnt[T] != 1 || Outputs.count(T))
+            return -1;
+        return (int)It->second;
+    };
+    // the other operand of a two-input node one of whose operands is the scalar `Want`, or of which one operand is T
+    auto beside = [&](int I, double Want, std::string* Other) {
+        const Node& N = Nodes[(size_t)I];
+        for (int Side = 0; Side < 2; ++Side)
+            if (scalar(N.In[(size_t)Side], Want)) { *Other = N.In[(size_t)(1 - Side)]; return true; }
+        return false;
+    };
+    auto partner = [&](int I, const std::string& T, std::string* Other) {
+        const Node& N = Nodes[(size_t)I];
+        for (int Side = 0; Side < 2; ++Side)
+            if (N.In[(size_t)Side] == T && N.In[(size_t)(1 - Side)] != T) { *Other = N.In[(size_t)(1 - Side)]; return true; }
+        return false;
+    };
+    auto become = [&](size_t K, const char* OpName, const std::string& X, std::vector<int> Absorbed) {
+        Node& N = Nodes[K];
+        std::sort(Absorbed.begin(), Absorbed.end());
+        std::string Name;
+        for (int I : Absorbed) {
+            Skip[(size_t)I] = true;
+            Name += Nodes[(size_t)I].Name + "+";
+        }
+        N.Name = Name + N.Name;
+        N.Op = OpName;
+        N.In = {X};
+    };
+    // x^3 of X as the tensor T: the nodes that compute it
+    auto cube = [&](const std::string& T, const std::string& X, std::vector<int>* Absorbed) {
+        const int IP = inner(T, "Pow", 2);
+        if (IP >= 0) {
+            if (Nodes[(size_t)IP].In[0] != X || !scalar(Nodes[(size_t)IP].In[1], 3.0)) return false;
+            Absorbed->push_back(IP);
+            return true;
+        }
+        const int IM = inner(T, "Mul", 2);
+        std::string Sq;
+        if (IM < 0 || !partner(IM, X, &Sq)) return false;
+        const int IS = inner(Sq, "Mul", 2);
+        if (IS < 0 || Nodes[(size_t)IS].In[0] != X || Nodes[(size_t)IS].In[1] != X) return false;
+        Absorbed->insert(Absorbed->end(), {IM, IS});
+        return true;
+    };
+    // tanh(sqrt(2/pi) (x + 0.044715 x^3)) + 1 as the tensor T
+    auto geluTail = [&](const std::string& T, const std::string& X, std::vector<int>* Absorbed) {
+        std::string Th, Arg, Sum, Cb, X3;
+        const int IA = inner(T, "Add", 2);
+        if (IA < 0 || !beside(IA, 1.0, &Th)) return false;
+        const int IT = inner(Th, "Tanh", 1);
+        if (IT < 0) return false;
+        const int IK = inner(Nodes[(size_t)IT].In[0], "Mul", 2);
+        if (IK < 0 || !beside(IK, 0.7978845608028654, &Sum)) return false;
+        const int IS = inner(Sum, "Add", 2);
+        if (IS < 0 || !partner(IS, X, &Cb)) return false;
+        const int IC = inner(Cb, "Mul", 2);
+        if (IC < 0 || !beside(IC, 0.044715, &X3) || !cube(X3, X, Absorbed)) return false;
+        Absorbed->insert(Absorbed->end(), {IA, IT, IK, IS, IC});
+        return true;
+    };
+    for (size_t K = 0; K < Nodes.size(); ++K) {
+        const Node& N = Nodes[K];
+        if (Skip[K] || N.In.size() != 2) continue;
+        if (N.Op == "Div") { // softsign
+            std::string Ab;
+            const int IA = inner(N.In[1], "Add", 2);
+            if (IA < 0 || !beside(IA, 1.0, &Ab)) continue;
+            const int IB = inner(Ab, "Abs", 1);
+            if (IB < 0 || Nodes[(size_t)IB].In[0] != N.In[0]) continue;
+            become(K, "Softsign", std::string(N.In[0]), {IA, IB});
+            continue;
+        }
+        if (N.Op != "Mul") continue;
+        bool Done = false;
+        for (int Side = 0; Side < 2 && !Done; ++Side) { // Mish: Mul(x, Tanh(Softplus(x)))
+            const std::string X = N.In[(size_t)Side];
+            const int IT = inner(N.In[(size_t)(1 - Side)], "Tanh", 1);
+            if (IT < 0) continue;
+            const int IS = inner(Nodes[(size_t)IT].In[0], "Softplus", 1);
+            if (IS < 0 || Nodes[(size_t)IS].In[0] != X) continue;
+            become(K, "MishAct", X, {IT, IS});
+            Done = true;
+        }
+        if (Done) continue;
+        // tanh-GELU: (x * tail) * 0.5, or (x * 0.5) * tail
+        std::string Prod, X;
+        if (beside((int)K, 0.5, &Prod)) {
+            const int IM = inner(Prod, "Mul", 2);
+            for (int Side = 0; Side < 2 && IM >= 0 && !Done; ++Side) {
+                std::vector<int> Absorbed = {IM};
+                X = Nodes[(size_t)IM].In[(size_t)Side];
+                if (!geluTail(Nodes[(size_t)IM].In[(size_t)(1 - Side)], X, &Absorbed)) continue;
+                become(K, "GeluTanh", X, Absorbed);
+                Done = true;
+            }
+            if (Done) continue;
+        }
+        for (int Side = 0; Side < 2 && !Done; ++Side) {
+            const int IH = inner(N.In[(size_t)Side], "Mul", 2);
+            if (IH < 0 || !beside(IH, 0.5, &X)) continue;
+            std::vector<int> Absorbed = {IH};
+            if (!geluTail(N.In[(size_t)(1 - Side)], X, &Absorbed)) continue;
+            become(K, "GeluTanh", X, Absorbed);
+            Done = true;
+        }
+    }
+}
+
 // ---- MaxPool / AveragePool that keep the board: one kLaunchPool.  A MaxPool whose window is the whole board (what the
 // exporter writes for adaptive_max_pool2d(x, 1)) is the global max: one kLaunchMax.
 void Planner::pool(const Node& N) {
@@ -1690,6 +1878,10 @@ void Planner::run() {
     for (const std::string& I : Ins)
         if (I != "input") throw Error("tensor contract: unexpected graph input '" + I + "'");
 
+    // (checked on the file's own nodes, before the rewrites below name theirs)
+    for (const Node& N : G.Nodes)
+        if (!opSet().count(N.Op) && N.Op != "Swish" && N.Op != "Gelu") fail(N, "op '" + N.Op + "' is outside the supported op set (DESIGN.md section 13)");
+
     // the swish rewrite: Mul(x, Sigmoid(x)) -> Swish(x) when the Sigmoid feeds only the Mul
     Nodes = G.Nodes;
     P.nodes = (int)Nodes.size();
@@ -1718,10 +1910,10 @@ void Planner::run() {
         }
     }
     rewriteGelu();
+    rewriteMath();
     for (size_t K = 0; K < Nodes.size(); ++K) {
         if (Skip[K]) continue;
         const Node& N = Nodes[K];
-        if (!opSet().count(N.Op) && N.Op != "Swish" && N.Op != "Gelu") fail(N, "op '" + N.Op + "' is outside the supported op set (DESIGN.md section 13)");
         for (const std::string& I : N.In)
             if (!I.empty()) {
                 ++Uses[I];
@@ -1794,6 +1986,7 @@ void Planner::run() {
             continue;
         }
         const Val& X = get(N, 0);
+        double PowOne = 0;
         if (formView(N) || attentionOp(N) || normOp(N, K)) continue;
         // [N,C,81] and the 4-D tensors exist only inside the patterns the calls above follow
         for (size_t J = 0; J < N.In.size(); ++J) {
@@ -1814,7 +2007,14 @@ void Planner::run() {
             layerNorm(N);
         } else if (Op == "Conv" || Op == "Gemm" || Op == "MatMul") {
             linear(N, K);
-        } else if (isAct(Op) || isBinary(Op) || isEltExtra(Op) || Op == "BatchNormalization") {
+        } else if (Op == "Pow" && powExponent(N, &PowOne) && PowOne == 1.0 && X.runtime) {
+            // x ** 1 is x: an open elementwise group read only here stays open under the new name
+            const bool MoveGroup = X.group >= 0 && absorbable(N.In[0]);
+            Val V = MoveGroup ? X : ready(N.In[0]);
+            V.producer = N.Name;
+            if (MoveGroup) Groups[(size_t)V.group].out = N.Out[0];
+            Vals[N.Out[0]] = V;
+        } else if (isAct(Op) || isBinary(Op) || isEltExtra(Op) || Op == "BatchNormalization" || Op == "Pow") {
             if (Op == "BatchNormalization" && !X.runtime) fail(N, "expected a runtime input");
             if (isBinary(Op) && !get(N, 0).runtime && !get(N, 1).runtime) fail(N, "constant operands only");
             elementwise(N);

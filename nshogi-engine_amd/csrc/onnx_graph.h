@@ -30,9 +30,12 @@ constexpr int kMaxCopySegs = 8; // sources of one channel concat
 
 // kActGelu: exact (erf); kActRelu6 = min(max(x, 0), 6); kActHardSigmoid = min(max(x / 6 + 0.5, 0), 1); kActHardSwish =
 // x * that.  All of them are parameter-free: a LeakyRelu, a PRelu, other Clip bounds are elementwise instructions.
+// kActRecip = 1 / x; kActMish = x tanh(softplus(x)); kActGeluTanh = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)));
+// kActSoftsign = x / (1 + |x|).
 enum Act {
     kActNone = 0, kActRelu, kActSigmoid, kActTanh, kActSwish, kActSoftplus, kActErf, kActGelu,
-    kActRelu6, kActHardSwish, kActHardSigmoid
+    kActRelu6, kActHardSwish, kActHardSigmoid,
+    kActExp, kActLog, kActSqrt, kActRecip, kActMish, kActGeluTanh, kActSoftsign
 };
 
 // A runtime tensor as a launch sees it.  buf: -1 = the plane buffer (graph input), >= 0 = activation buffer.
@@ -46,7 +49,10 @@ struct View {
 
 // Elementwise program: registers r0..r15; opcodes below.  LOAD reads source `a` into register `dst`.
 // kEltLeaky: dst = a > 0 ? a : a * b (LeakyRelu: b holds alpha; PRelu: b holds the channel's slope); kEltNeg, kEltAbs: of a.
-enum EltOp { kEltLoad = 0, kEltAct, kEltAdd, kEltSub, kEltMul, kEltDiv, kEltMax, kEltMin, kEltLeaky, kEltNeg, kEltAbs };
+// kEltPow: dst = powf(a, b), b loaded from a scalar source: a Pow whose exponent has no exact form.
+enum EltOp {
+    kEltLoad = 0, kEltAct, kEltAdd, kEltSub, kEltMul, kEltDiv, kEltMax, kEltMin, kEltLeaky, kEltNeg, kEltAbs, kEltPow
+};
 struct EltInstr {
     uint8_t op, dst, a, b; // kEltAct: a = source register, b = Act; binary: dst = a (op) b; unary: b unused
 };

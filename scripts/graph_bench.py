@@ -12,6 +12,7 @@
     python scripts/graph_bench.py --norm [--out profiles/graph/norm_bench.json]   # the GroupNorm row
     python scripts/graph_bench.py --trace-norm      # GroupNorm at three group counts, a max pool and a depthwise 3x3
     python scripts/graph_bench.py --summarize-norm DIR/run_results.db [--out profiles/graph/norm_bench.json]
+    python scripts/graph_bench.py --mish [--out profiles/graph/mish_bench.json] [--repeats 3]   # the Mish row
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
@@ -30,6 +31,10 @@ more work) and the forced family net (graphConv<9>, which must not move), all in
 B = 512 and C = 256, a bare GroupNorm of 32 groups, of 256 groups (instance norm) and of one group (graphGroupNorm), a
 3x3 max pool (graphPool) and a bare depthwise 3x3 (graphDepthwise): five kernels that each read and write the same
 84.9 MB.  --summarize-norm prints their medians and ranges and adds them to the --norm file.
+
+--mish: the 20x256 residual net with Mish for every ReLU (tests/golden/make_onnx_math_golden.py's MishBenchNet: every
+Mish rides in a conv's launch), the same net with swish, and the 20x256 family net forced onto the general path, each
+timed `--repeats` times in turn; the file holds every repeat, so the run's spread is in it.
 
 --attention: a pre-LN transformer over the 81 squares (tests/golden/make_onnx_attention_golden.py's PreNet with 8
 blocks, F = 256, H = 8 heads of d = 32, FFN width 1024), exported at run time, on the general path.
@@ -103,6 +108,14 @@ def depthwise3_onnx(path):
     import make_onnx_geometry_golden as mk
     torch.manual_seed(9)
     mk.export_model(mk.randomize(mk.DwNet(256, 3, full=False), 17).eval(), path)
+
+
+def mish_onnx(path, swish=False):
+    import torch
+    import torch.nn.functional as Fn
+    import make_onnx_math_golden as mk
+    torch.manual_seed(13)
+    mk.export_model(mk.randomize(mk.MishBenchNet(C=86, F=256, blocks=20, act=Fn.silu if swish else Fn.mish), 21).eval(), path)
 
 
 def attention_onnx(path):
@@ -292,6 +305,8 @@ def main():
     ap.add_argument("--norm", action="store_true", help="the 20x256 net with GroupNorm(32)-ReLU on the general path")
     ap.add_argument("--trace-norm", action="store_true", help="GroupNorm of 32, 256 and 1 groups, a 3x3 max pool and a depthwise 3x3 at B=512, C=256")
     ap.add_argument("--summarize-norm", metavar="DB", help="summarise the rocprofv3 database of a --trace-norm run")
+    ap.add_argument("--mish", action="store_true", help="the 20x256 net with Mish, the same net with swish, and the forced family net")
+    ap.add_argument("--repeats", type=int, default=3, help="--mish: times each (net, batch) is timed")
     a = ap.parse_args()
     if a.summarize_norm:
         summarize_norm(a.summarize_norm, a.out.replace("graph_bench.json", "norm_bench.json"))
@@ -315,6 +330,25 @@ def main():
             make(path)
             r, info = rate(nsg, path, TRACE_BATCH, iters=POOL_FAMILY_FORWARDS - 3, warmup=3)
             print(json.dumps({label: r, "launches": info["launches"]}), flush=True)
+        return
+    if a.mish:
+        paths = {k: os.path.join(tmp, k + ".onnx") for k in ("mish_20x256_general", "swish_20x256_general", "family_20x256_general")}
+        mish_onnx(paths["mish_20x256_general"])
+        mish_onnx(paths["swish_20x256_general"], swish=True)
+        family_onnx(nsg, paths["family_20x256_general"])
+        rows = {k: {} for k in paths}
+        for b in [int(b) for b in a.batches.split(",")]:
+            for rep in range(a.repeats):  # the nets in turn, so that drift of the clock falls on all of them
+                for k, path in paths.items():
+                    r, info = rate(nsg, path, b, force=k.startswith("family"), iters=20 if b >= 256 else 50)
+                    rows[k].setdefault(str(b), []).append(round(r, 1))
+                    rows[k].update(path=info["path"], launches=info["launches"], conv_launches=info["conv_launches"])
+        for k, row in rows.items():
+            print(k, json.dumps(row), flush=True)
+        out = a.out.replace("graph_bench.json", "mish_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump({"repeats": a.repeats, "rows": rows}, f, indent=1)
         return
     if a.norm:
         nm = os.path.join(tmp, "norm_20x256.onnx")
