@@ -10,6 +10,8 @@
 #include <cstring>
 #include <limits>
 #include <new>
+#include <stdexcept>
+#include <string>
 
 namespace nshogi {
 namespace engine {
@@ -61,6 +63,90 @@ class Arena {
 
 } // namespace
 
+// Decision log (--decision-log), format version 1.  A text file: the first line is "nsg-decision-log 1",
+// every further line is one record, its fields separated by single spaces.  A record starts with
+//     <type> <game id> <ply of the root being searched> <playouts of this game so far>
+// Counts and indices are decimal.  A float is its bit pattern: f32 as 8 hex digits, f64 as 16.  An array is ONE
+// field, its elements' bit patterns run together (u32 as 8 hex digits; flags as one '0'/'1' character each); an
+// empty array is "-".  "Visited" arrays hold an entry only for the children with visits > 0, in child order.
+// After the four leading fields:
+//   evaluation     N gumbel full-search leaf-is-root win:f32 draw:f32 logits:f32[N] softmax:f32[N]|- gamma:f64[N]|-
+//                  gamma-sum:f64|- priors:f32[N]|=          (softmax: before the mix; "-" where none is taken;
+//                                                           priors "=": bit for bit the softmax field)
+//   select         depth parent-visits draw-value:f32 N priors:f32[N] visits:u32[N] win-sums:f64[visited]
+//                  draw-sums:f64[visited] chosen            (draw value: of the side to move at the parent)
+//   gumbel-select  halving-playouts N targets:flag[N] visits:u32[N] chosen
+//   search-start   budget num-sampling halving-playouts     (Gumbel mode only)
+//   sample         num-sampling N noise:f64[N] priors:f32[N] targets:flag[N]
+//   halve          draw-value:f32 halving-count num-sampling N targets:flag[N], then for the targets only
+//                  visits:u32[] win-sums:f64[] draw-sums:f64[] priors:f32[] noise:f64[], then budget root-visits
+//                  halving-playouts, and after the round: kept survivors:flag[N] halving-playouts goes-on
+//   transition     mode(0 most visited, 1 Gumbel) draw-value:f32 N visits:u32[N] win-sums:f64[visited]
+//                  draw-sums:f64[visited] priors:f32[N] targets:flag[N]|- noise:f64[N]|- chosen move16
+// The records of one game are in the order of its decisions; games interleave.  select and gumbel-select are
+// written for every K-th selection of a game (--decision-log-every), every other type always.
+class DecisionLog::Slot {
+ public:
+    uint64_t Playouts = 0, Selections = 0; // of the game being played in this slot
+    // finishEvaluation overwrites the logits in place: what the record needs of them
+    float Raw[600], Softmax[600];
+    bool HasSoftmax = false, HasGamma = false;
+    double GammaSum = 0.0;
+
+    bool nextSelectionIsRecorded(int Every) { return Selections++ % (uint64_t)Every == 0; }
+    void begin(const char* Type, uint64_t Game, int Ply) {
+        Text += Type;
+        num(Game); num((uint64_t)Ply); num(Playouts);
+    }
+    void num(uint64_t V) { Text += ' '; Text += std::to_string(V); }
+    void f32(float V) { Text += ' '; e32(V); }
+    void f64(double V) { Text += ' '; e64(V); }
+    void none() { Text += " -"; }
+    void same() { Text += " ="; }
+    // elements of an array field, written from inside array()
+    void e32(float V) { uint32_t B; std::memcpy(&B, &V, 4); hex(B, 8); }
+    void e64(double V) { uint64_t B; std::memcpy(&B, &V, 8); hex(B, 16); }
+    void eu(uint32_t V) { hex(V, 8); }
+    void flag(bool V) { Text += V ? '1' : '0'; }
+    template <class Fill> void array(Fill&& F) {
+        Text += ' ';
+        const std::size_t At = Text.size();
+        F();
+        if (Text.size() == At) Text += '-';
+    }
+    void end(DecisionLog& Out) {
+        Text += '\n';
+        if (Text.size() >= (std::size_t)1 << 16) flush(Out);
+    }
+    void flush(DecisionLog& Out) {
+        if (Text.empty()) return;
+        Out.append(Text);
+        Text.clear();
+    }
+
+ private:
+    void hex(uint64_t V, int Digits) {
+        char B[16];
+        for (int I = Digits - 1; I >= 0; --I, V >>= 4) B[I] = "0123456789abcdef"[V & 15];
+        Text.append(B, (std::size_t)Digits);
+    }
+    std::string Text; // whole records not yet in the file
+};
+
+DecisionLog::DecisionLog(const std::string& Path) : Out(std::fopen(Path.c_str(), "wb")) {
+    if (!Out) throw std::runtime_error("cannot open decision log " + Path);
+    std::fputs("nsg-decision-log 1\n", Out);
+}
+
+DecisionLog::~DecisionLog() {
+    if (Out) std::fclose(Out);
+}
+
+void DecisionLog::append(const std::string& Lines) {
+    std::lock_guard<std::mutex> Lock(Mutex);
+    std::fwrite(Lines.data(), 1, Lines.size(), Out);
+}
+
 class Game {
  public:
     // Slot: this game slot's number among the run's Stride concurrent slots; its k-th game has id Slot + k * Stride
@@ -96,6 +182,11 @@ class Game {
             }
         }
         return false;
+    }
+
+    // (decision log) hands the records this slot still holds to the file
+    void flushDecisions() {
+        if (Dec) Dec->flush(*Eng->Decisions);
     }
 
     // (leaf log) the position and StateConfig of the leaf waiting for its evaluation
@@ -149,6 +240,7 @@ class Game {
             Config.WhiteDrawValue = 1.0f - Config.BlackDrawValue;
         }
         GameMoves = 0;
+        if (Dec) Dec->Playouts = Dec->Selections = 0;
         MoveHistory.clear();
         FullSearchAt.clear();
         Ph = Phase::RootPreparation;
@@ -160,6 +252,7 @@ class Game {
         Tree.rewind();
         Root = newNode(nullptr);
         RootPly = S.ply();
+        if (Eng->Decisions && !Dec) Dec = std::make_unique<DecisionLog::Slot>();
         MoveList L;
         S.generateLegalMoves(L);
         const bool Gumbel = Eng->Opt.Gumbel;
@@ -181,6 +274,7 @@ class Game {
             const double Init = std::floor((double)Budget / (std::log2((double)NumSampling) * (double)NumSampling));
             HalvingPlayouts = (uint32_t)std::max(1.0, Init);
             HalvingCount = 1;
+            if (Dec) logSearchStart();
         }
         Ph = Phase::LeafSelection;
     }
@@ -281,6 +375,7 @@ class Game {
         if (Root->NumChildren == 1) { Ph = Phase::Transition; return; }
         if (Leaf == Root) {
             sampleTopMMoves();
+            if (Dec) logSample();
         } else {
             uint32_t MinN = std::numeric_limits<uint32_t>::max();
             for (uint16_t I = 0; I < Root->NumChildren; ++I) {
@@ -291,8 +386,11 @@ class Game {
             }
             if (MinN >= HalvingPlayouts) {
                 if (Root->Visits >= Budget + 1) { Ph = Phase::Transition; return; }
+                if (Dec) logHalveBefore();
                 const uint16_t NumValid = executeSequentialHalving();
-                if (!updateHalvingSchedule(NumValid)) { Ph = Phase::Transition; return; }
+                const bool GoesOn = updateHalvingSchedule(NumValid);
+                if (Dec) logHalveAfter(NumValid, GoesOn);
+                if (!GoesOn) { Ph = Phase::Transition; return; }
             }
         }
         Ph = Phase::LeafSelection;
@@ -304,7 +402,12 @@ class Game {
         for (;;) {
             if (N->Visits == 0 || N->NumChildren == 0 || N->Repetition != 0) break;
             if (S.ply() >= Config.MaxPly) break;
-            Edge* E = (Eng->Opt.Gumbel && N == Root) ? pickGumbelRootEdge() : pickEdge(N);
+            const bool AtGumbelRoot = Eng->Opt.Gumbel && N == Root;
+            Edge* E = AtGumbelRoot ? pickGumbelRootEdge() : pickEdge(N);
+            if (Dec && Dec->nextSelectionIsRecorded(Eng->Opt.DecisionLogEvery)) {
+                if (AtGumbelRoot) logGumbelSelect(E);
+                else logSelect(N, E);
+            }
             S.doMove(S.moveFrom16(E->Move16));
             if (!E->Child) E->Child = newNode(N);
             N = E->Child;
@@ -372,10 +475,15 @@ class Game {
     // softmax over the legal-move logits, Dirichlet noise at a full-search root
     // (frame.cc:113-135), priors into the edges
     void finishEvaluation(uint16_t N, float Win, float Draw) {
+        if (Dec) {
+            std::memcpy(Dec->Raw, Logits, N * sizeof(float));
+            Dec->HasSoftmax = Dec->HasGamma = false;
+        }
         if (Eng->Opt.Gumbel && Leaf == Root) { // frame.cc:116: a Gumbel root keeps the raw logits
             for (uint16_t I = 0; I < N; ++I) Leaf->Edges[I].Prior = Logits[I];
             Leaf->WinPred = Win;
             Leaf->DrawPred = Draw;
+            if (Dec) logEvaluation(N, Win, Draw);
             Ph = Phase::Backpropagation;
             return;
         }
@@ -387,6 +495,10 @@ class Game {
             Sum += Logits[I];
         }
         for (uint16_t I = 0; I < N; ++I) Logits[I] /= Sum;
+        if (Dec) {
+            std::memcpy(Dec->Softmax, Logits, N * sizeof(float));
+            Dec->HasSoftmax = true;
+        }
         if (Leaf == Root && FullSearch) {
             std::gamma_distribution<double> Gamma(0.15, 1.0); // worker.cc:650-652
             double NoiseSum = 0.0;
@@ -395,6 +507,10 @@ class Game {
                 NoiseSum += Noise[I];
             }
             if (NoiseSum <= 0.0) NoiseSum = 1.0;
+            if (Dec) {
+                Dec->HasGamma = true;
+                Dec->GammaSum = NoiseSum;
+            }
             constexpr double Eps = 0.25;
             for (uint16_t I = 0; I < N; ++I)
                 Logits[I] = (float)((1 - Eps) * (double)Logits[I] + Eps * Noise[I] / NoiseSum);
@@ -402,6 +518,7 @@ class Game {
         for (uint16_t I = 0; I < N; ++I) Leaf->Edges[I].Prior = Logits[I];
         Leaf->WinPred = Win;
         Leaf->DrawPred = Draw;
+        if (Dec) logEvaluation(N, Win, Draw);
         Ph = Phase::Backpropagation;
     }
 
@@ -415,6 +532,7 @@ class Game {
         }
         undoToRoot();
         ++Ctx->St.Playouts;
+        if (Dec) ++Dec->Playouts;
         if (Eng->Opt.Gumbel) gumbelAfterBackprop();
         else if (Root->NumChildren == 1 || Root->Visits >= Budget) Ph = Phase::Transition;
         else Ph = Phase::LeafSelection;
@@ -432,6 +550,7 @@ class Game {
                     if (Sc > BestScore) { BestScore = Sc; Pick = &Root->Edges[I]; }
                 }
             }
+            if (Dec) logTransition(true, Pick);
             playMove(S.moveFrom16(Pick->Move16));
             return;
         }
@@ -452,6 +571,7 @@ class Game {
                 Best = E;
             }
         }
+        if (Dec) logTransition(false, Best);
         playMove(S.moveFrom16(Best->Move16));
     }
 
@@ -472,6 +592,7 @@ class Game {
         Ctx->St.MovesOfFinishedGames += GameMoves;
         if (Eng->Teacher) Ctx->St.TeacherRecords += Eng->Teacher->saveGame(MoveHistory, FullSearchAt, Config, Winner);
         if (Eng->Log) Eng->Log->add(GameId, Winner, MoveHistory);
+        flushDecisions();
         newGame();
     }
 
@@ -510,6 +631,112 @@ class Game {
         Ph = Phase::RootPreparation;
     }
 
+    // ---- decision log: one function per record type (format: DecisionLog::Slot).  Only called with Dec set.
+    static uint32_t visitsOf(const Edge& E) { return E.Child ? E.Child->Visits : 0; }
+    bool isTarget(uint16_t I) const { return I < IsTarget.size() && IsTarget[I]; }
+
+    // priors, visits and -- for the visited children -- the sums the win-rate blend reads
+    void logChildren(const Node* N, bool PriorsFirst) const {
+        const uint16_t C = N->NumChildren;
+        auto Priors = [&]() { Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) Dec->e32(N->Edges[I].Prior); }); };
+        if (PriorsFirst) Priors();
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) Dec->eu(visitsOf(N->Edges[I])); });
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) if (visitsOf(N->Edges[I])) Dec->e64(N->Edges[I].Child->WinSum); });
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) if (visitsOf(N->Edges[I])) Dec->e64(N->Edges[I].Child->DrawSum); });
+        if (!PriorsFirst) Priors();
+    }
+    void logTargets(uint16_t C) const {
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) Dec->flag(isTarget(I)); });
+    }
+
+    void logEvaluation(uint16_t N, float Win, float Draw) const {
+        Dec->begin("evaluation", GameId, RootPly);
+        Dec->num(N); Dec->num(Eng->Opt.Gumbel); Dec->num(FullSearch); Dec->num(Leaf == Root);
+        Dec->f32(Win); Dec->f32(Draw);
+        Dec->array([&]() { for (uint16_t I = 0; I < N; ++I) Dec->e32(Dec->Raw[I]); });
+        Dec->array([&]() { if (Dec->HasSoftmax) for (uint16_t I = 0; I < N; ++I) Dec->e32(Dec->Softmax[I]); });
+        Dec->array([&]() { if (Dec->HasGamma) for (uint16_t I = 0; I < N; ++I) Dec->e64(Noise[I]); });
+        if (Dec->HasGamma) Dec->f64(Dec->GammaSum);
+        else Dec->none();
+        bool AsSoftmax = Dec->HasSoftmax; // most evaluations: no mix, and a third of the record saved
+        for (uint16_t I = 0; AsSoftmax && I < N; ++I) AsSoftmax = !std::memcmp(&Leaf->Edges[I].Prior, &Dec->Softmax[I], sizeof(float));
+        if (AsSoftmax) Dec->same();
+        else Dec->array([&]() { for (uint16_t I = 0; I < N; ++I) Dec->e32(Leaf->Edges[I].Prior); });
+        Dec->end(*Eng->Decisions);
+    }
+
+    void logSelect(const Node* N, const Edge* Chosen) const {
+        Dec->begin("select", GameId, RootPly);
+        Dec->num((uint64_t)(S.ply() - RootPly)); Dec->num(N->Visits); Dec->f32(drawValue(S.sideToMove()));
+        Dec->num(N->NumChildren);
+        logChildren(N, true);
+        Dec->num((uint64_t)(Chosen - N->Edges));
+        Dec->end(*Eng->Decisions);
+    }
+
+    void logGumbelSelect(const Edge* Chosen) const {
+        const uint16_t C = Root->NumChildren;
+        Dec->begin("gumbel-select", GameId, RootPly);
+        Dec->num(HalvingPlayouts); Dec->num(C);
+        logTargets(C);
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) Dec->eu(visitsOf(Root->Edges[I])); });
+        Dec->num((uint64_t)(Chosen - Root->Edges));
+        Dec->end(*Eng->Decisions);
+    }
+
+    void logSearchStart() const {
+        Dec->begin("search-start", GameId, RootPly);
+        Dec->num(Budget); Dec->num(NumSampling); Dec->num(HalvingPlayouts);
+        Dec->end(*Eng->Decisions);
+    }
+
+    void logSample() const {
+        const uint16_t C = Root->NumChildren;
+        Dec->begin("sample", GameId, RootPly);
+        Dec->num(NumSampling); Dec->num(C);
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) Dec->e64(Noise[I]); });
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) Dec->e32(Root->Edges[I].Prior); });
+        logTargets(C);
+        Dec->end(*Eng->Decisions);
+    }
+
+    // the round's inputs, before executeSequentialHalving and updateHalvingSchedule change them ...
+    void logHalveBefore() const {
+        const uint16_t C = Root->NumChildren;
+        Dec->begin("halve", GameId, RootPly);
+        Dec->f32(drawValue(S.sideToMove())); Dec->num(HalvingCount); Dec->num(NumSampling); Dec->num(C);
+        logTargets(C);
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) if (isTarget(I)) Dec->eu(visitsOf(Root->Edges[I])); });
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) if (isTarget(I)) Dec->e64(Root->Edges[I].Child->WinSum); });
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) if (isTarget(I)) Dec->e64(Root->Edges[I].Child->DrawSum); });
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) if (isTarget(I)) Dec->e32(Root->Edges[I].Prior); });
+        Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) if (isTarget(I)) Dec->e64(Noise[I]); });
+        Dec->num(Budget); Dec->num(Root->Visits); Dec->num(HalvingPlayouts);
+    }
+    // ... and what they decided, which ends the record
+    void logHalveAfter(uint16_t Kept, bool GoesOn) const {
+        Dec->num(Kept);
+        logTargets(Root->NumChildren);
+        Dec->num(HalvingPlayouts); Dec->num(GoesOn);
+        Dec->end(*Eng->Decisions);
+    }
+
+    void logTransition(bool GumbelMode, const Edge* Chosen) const {
+        const uint16_t C = Root->NumChildren;
+        Dec->begin("transition", GameId, RootPly);
+        Dec->num(GumbelMode); Dec->f32(drawValue(S.sideToMove())); Dec->num(C);
+        logChildren(Root, false);
+        if (GumbelMode) {
+            logTargets(C);
+            Dec->array([&]() { for (uint16_t I = 0; I < C; ++I) Dec->e64(Noise[I]); });
+        } else {
+            Dec->none(); Dec->none();
+        }
+        Dec->num((uint64_t)(Chosen - Root->Edges)); Dec->num(Chosen->Move16);
+        Dec->end(*Eng->Decisions);
+    }
+
+    std::unique_ptr<DecisionLog::Slot> Dec; // this slot's share of the decision log; null unless one is written
     std::atomic<bool> SolverDone{false};
     Move SolverMove;
     uint64_t SolverNodes = 0;
@@ -756,6 +983,9 @@ void Engine::step() {
 
 void Engine::drain() {
     for (int G = 0; G < 2; ++G) apply(*Groups[G]);
+    if (Decisions)
+        for (int G = 0; G < 2; ++G)
+            for (auto& Gm : Groups[G]->Games) Gm->flushDecisions();
 }
 
 void Engine::run(const std::atomic<bool>* Stop, uint64_t MaxFinishedGames) {

@@ -46,11 +46,13 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <cstdio>
 #include <deque>
 #include <mutex>
 #include <memory>
 #include <functional>
 #include <random>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -79,6 +81,7 @@ struct Options {
     int SolverThreads = 0;
     uint64_t DfpnNodes = 100000; // node budget of the df-pn mate solver run after every move (worker.cc:516); 0 = off
     bool MateSearch = true;      // mate-in-3 search by checks at every non-root leaf (worker.cc:349-358)
+    int DecisionLogEvery = 1;    // --decision-log-every: with a DecisionLog set, every K-th selection of a game is recorded
 };
 
 struct Stats {
@@ -120,6 +123,23 @@ class TeacherWriter; // teacher.h
 class GameLog;       // teacher.h: one line per finished game
 class LeafLog;       // teacher.h: test hook, one line per packed leaf
 
+// --decision-log: every search decision with everything it read, for tests/selfplay_ref.py to recompute
+// (the format is described at the writer, selfplay.cc).  One file shared by the engines of a process; a game
+// slot collects its records in a Slot of its own and appends them, whole lines, under the one lock.
+class DecisionLog {
+ public:
+    class Slot; // selfplay.cc
+    explicit DecisionLog(const std::string& Path);
+    ~DecisionLog();
+    DecisionLog(const DecisionLog&) = delete;
+    DecisionLog& operator=(const DecisionLog&) = delete;
+    void append(const std::string& Lines);
+
+ private:
+    std::FILE* Out = nullptr;
+    std::mutex Mutex;
+};
+
 // One engine = one search thread's worth of games + its two executors.
 class Engine {
  public:
@@ -140,6 +160,7 @@ class Engine {
     void setTeacherWriter(TeacherWriter* W) { Teacher = W; }
     void setGameLog(GameLog* L) { Log = L; }
     void setLeafLog(LeafLog* L) { Leaves = L; }
+    void setDecisionLog(DecisionLog* L) { Decisions = L; }
 
     // Progress counters another thread may read while run() is going (the driver's rate timeline)
     uint64_t publishedFinished() const { return PubFinished.load(std::memory_order_relaxed); }
@@ -174,6 +195,7 @@ class Engine {
     TeacherWriter* Teacher = nullptr;
     GameLog* Log = nullptr;
     LeafLog* Leaves = nullptr;
+    DecisionLog* Decisions = nullptr;
     uint64_t EngineIndexForLogs = 0;
     std::vector<std::unique_ptr<WorkerCtx>> Ctx;
     std::vector<std::thread> Pool;

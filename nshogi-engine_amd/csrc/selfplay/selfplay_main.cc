@@ -30,7 +30,12 @@
 //                 [--game-log games.txt] (one line per finished game: id winner plies digest moves)
 //                 [--leaf-log leaves.txt] (tests: every leaf of every batch -- batch no., slot, SFEN, StateConfig, the
 //                                          1376 bytes the engine packed into that slot)
+//                 [--decision-log decisions.txt] [--decision-log-every 1]
+//                                        (tests: every search decision with the numbers it read, bit for bit -- the
+//                                         evaluation's softmax and noise mix, every K-th edge selection of a game, the
+//                                         Gumbel sampling and halving rounds, the move played; format: selfplay.cc)
 //                 --executor hash: test executor whose outputs are a checksum of the position's own bitboards
+//                 --help: the options and their defaults
 #include "selfplay.h"
 #include "teacher.h"
 
@@ -79,8 +84,31 @@ class HashInfer : public infer::Infer {
 };
 } // namespace
 
+const char* const Usage =
+    "usage: selfplay [option value]...\n"
+    "  --executor hip|random|zero|hash   evaluator (hip); hash: test executor, a checksum of the position\n"
+    "  --weights FILE                    model.onnx or file.nsgw (hip)\n"
+    "  --gpu N (0)  --num-gpus N (1)  --gpu-map a,b,...   devices of the GPU shards\n"
+    "  --threads N (2)                   engines per GPU, each with two batches in flight\n"
+    "  --workers N (1)                   host threads per engine advancing its games\n"
+    "  --solver-threads N (0)            threads per engine for the df-pn call after a move, 0 = inline\n"
+    "  --games-per-group N (256)         concurrent games per group, two groups per engine\n"
+    "  --playouts N (800)  --full-search-ratio R (0.25)\n"
+    "  --gumbel 0|1 (0)  --num-sampling-moves M (16)\n"
+    "  --seconds S (30)  --max-games N (0 = run for --seconds)  --seed N (0)\n"
+    "  --precision N  --mate-search 0|1 (1)  --dfpn-nodes N (100000)\n"
+    "  --evaluation-cache-memory-size MB (1024, per GPU shard; 0 = none)  --share-evaluation-cache 0|1 (0)\n"
+    "  --numa 0|1 (0)\n"
+    "  --teacher FILE                    training records of finished games\n"
+    "  --game-log FILE                   one line per finished game\n"
+    "  --leaf-log FILE                   tests: every leaf of every batch as packed\n"
+    "  --decision-log FILE               tests: every search decision with the numbers it read, bit for bit\n"
+    "  --decision-log-every K (1)        ... but only every K-th edge selection of a game\n";
+
 int main(int Argc, char* Argv[]) {
-    std::string Executor = "hip", Weights, TeacherPath, GameLogPath, LeafLogPath;
+    for (int I = 1; I < Argc; ++I)
+        if (!std::strcmp(Argv[I], "--help") || !std::strcmp(Argv[I], "-h")) { std::cout << Usage; return 0; }
+    std::string Executor = "hip", Weights, TeacherPath, GameLogPath, LeafLogPath, DecisionLogPath;
     int Gpu = 0, NumGpus = 1, Threads = 2, Precision = NSG_PRECISION_F16X3;
     std::vector<int> GpuMap;
     double Seconds = 30.0;
@@ -96,6 +124,8 @@ int main(int Argc, char* Argv[]) {
         else if (K == "--teacher") TeacherPath = V;
         else if (K == "--game-log") GameLogPath = V;
         else if (K == "--leaf-log") LeafLogPath = V;
+        else if (K == "--decision-log") DecisionLogPath = V;
+        else if (K == "--decision-log-every") Opt.DecisionLogEvery = std::stoi(V);
         else if (K == "--dfpn-nodes") Opt.DfpnNodes = std::stoull(V);
         else if (K == "--gpu") Gpu = std::stoi(V);
         else if (K == "--num-gpus") NumGpus = std::stoi(V);
@@ -128,6 +158,7 @@ int main(int Argc, char* Argv[]) {
         else { std::cerr << "unknown option " << K << std::endl; return 2; }
     }
     if (!GpuMap.empty() && (int)GpuMap.size() != NumGpus) { std::cerr << "--gpu-map needs one device per --num-gpus shard" << std::endl; return 2; }
+    if (Opt.DecisionLogEvery < 1) { std::cerr << "--decision-log-every needs a positive count" << std::endl; return 2; }
     if (NumGpus < 1 || Threads < 1 || Opt.GamesPerGroup < 1) { std::cerr << "bad --num-gpus/--threads/--games-per-group" << std::endl; return 2; }
     const bool Hip = Executor == "hip";
     const int NumEngines = NumGpus * Threads;
@@ -174,6 +205,8 @@ int main(int Argc, char* Argv[]) {
     if (!GameLogPath.empty()) Log = std::make_unique<selfplay::GameLog>(GameLogPath);
     std::unique_ptr<selfplay::LeafLog> Leaves;
     if (!LeafLogPath.empty()) Leaves = std::make_unique<selfplay::LeafLog>(LeafLogPath);
+    std::unique_ptr<selfplay::DecisionLog> Decisions;
+    if (!DecisionLogPath.empty()) Decisions = std::make_unique<selfplay::DecisionLog>(DecisionLogPath);
     // Every engine is built on the thread that runs it: with --numa the thread is first bound to its
     // GPU shard's NUMA node, so the engine's pinned batch buffers are first-touched there.
     std::vector<std::unique_ptr<selfplay::Engine>> Engines((std::size_t)NumEngines);
@@ -192,6 +225,7 @@ int main(int Argc, char* Argv[]) {
             Engines[(std::size_t)E]->setTeacherWriter(Teacher.get());
             Engines[(std::size_t)E]->setGameLog(Log.get());
             Engines[(std::size_t)E]->setLeafLog(Leaves.get());
+            Engines[(std::size_t)E]->setDecisionLog(Decisions.get());
             ++Built;
             while (!Go.load(std::memory_order_acquire)) std::this_thread::yield();
             Engines[(std::size_t)E]->run(&Stop, PerEngineGames);
