@@ -1,0 +1,124 @@
+// plan_dump.cc -- prints every field of the GraphPlan the planner returns for each model, as text: the planner's
+// output pinned on the CPU (tests/test_plan_snapshot.py compares it with tests/golden/graph_plans.txt).
+//   plan_dump [--planes N] MODEL.onnx ... [--planes M] MODEL.onnx ...     (N: the input planes, 86 until given)
+// Uses the public onnx_graph.h only.  Floats print as %a and doubles as %.17g, so every bit shows; no path beyond the
+// model's base name and no timing appears: two runs print the same bytes.
+#include "onnx_graph.h"
+
+#include <algorithm>
+#include <cinttypes>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+
+using namespace nsg::graph;
+
+namespace {
+
+uint64_t hashFloats(const std::vector<float>& W, size_t Begin, size_t End) { // FNV-1a over the bytes
+    uint64_t H = 1469598103934665603ull;
+    const unsigned char* P = (const unsigned char*)W.data();
+    for (size_t K = Begin * 4; K < End * 4; ++K) H = (H ^ P[K]) * 1099511628211ull;
+    return H;
+}
+
+void view(const char* Name, const View& V) {
+    std::printf(" %s=%d/%d/%d/%d/%c", Name, V.buf, V.stride, V.offset, V.C, V.spatial ? 's' : 'f');
+}
+
+// the offsets into `weights` a launch reads its constants at
+std::vector<size_t> constsOf(const Launch& L) {
+    std::vector<size_t> R;
+    const int K = L.kind;
+    if (K == kLaunchConv || K == kLaunchLayerNorm || K == kLaunchGroupNorm) R = {L.wOff, L.biasOff};
+    if (K == kLaunchRmsNorm) R = {L.wOff};
+    if (K == kLaunchAttention && L.hasBias) R = {L.biasOff};
+    for (const EltSrc& S : L.srcs)
+        if (S.mode == kSrcChannel || S.mode == kSrcSquareChannel) R.push_back(S.constOff);
+    return R;
+}
+
+void dump(const GraphPlan& P) {
+    std::printf("numChannels=%d planeStride=%d nodes=%d convLaunches=%d attentionLaunches=%d params=%" PRIu64
+                " flopsPerPosition=%.17g activationBytesPerPosition=%zu\n",
+                P.numChannels, P.planeStride, P.nodes, P.convLaunches, P.attentionLaunches, P.params, P.flopsPerPosition,
+                P.activationBytesPerPosition);
+    std::printf("weights=%zu hash=%016" PRIx64 "\n", P.weights.size(), hashFloats(P.weights, 0, P.weights.size()));
+    std::printf("bufSpatialStride");
+    for (int S : P.bufSpatialStride) std::printf(" %d", S);
+    std::printf("\nbufFlatStride");
+    for (int S : P.bufFlatStride) std::printf(" %d", S);
+    std::printf("\nlaunches=%zu\n", P.launches.size());
+    // a constant record runs from its offset to the next offset any launch names
+    std::vector<size_t> Starts;
+    for (const Launch& L : P.launches)
+        for (size_t O : constsOf(L)) Starts.push_back(O);
+    Starts.push_back(P.weights.size());
+    std::sort(Starts.begin(), Starts.end());
+    for (size_t I = 0; I < P.launches.size(); ++I) {
+        const Launch& L = P.launches[I];
+        std::printf("#%zu kind=%d name=%s", I, L.kind, L.name.c_str());
+        view("out", L.out);
+        view("in", L.in);
+        view("res", L.res);
+        std::printf(" dense=%d depthwise=%d taps=%d k=%dx%d d=%dx%d cinPad=%d coutTiles=%d wOff=%zu biasOff=%zu act=%d eltOut=%d"
+                    " poolMode=%d eps=%a groups=%d",
+                    L.dense, L.depthwise, L.taps, L.kh, L.kw, L.dh, L.dw, L.cinPad, L.coutTiles, L.wOff, L.biasOff, L.act,
+                    L.eltOut, L.poolMode, (double)L.eps, L.groups);
+        view("attK", L.attK);
+        view("attV", L.attV);
+        std::printf(" heads=%d headDim=%d scale=%a hasBias=%d", L.heads, L.headDim, (double)L.scale, L.hasBias);
+        std::printf(" srcs=%zu", L.srcs.size());
+        for (const EltSrc& S : L.srcs) {
+            std::printf(" [mode=%d", S.mode);
+            view("v", S.v);
+            std::printf(" constOff=%zu scalar=%a]", S.constOff, (double)S.scalar);
+        }
+        std::printf(" code=%zu", L.code.size());
+        for (const EltInstr& C : L.code) std::printf(" %d:%d,%d,%d", C.op, C.dst, C.a, C.b);
+        std::printf(" segs=%zu", L.segs.size());
+        for (const CopySeg& S : L.segs) {
+            std::printf(" [dstOff=%d", S.dstOff);
+            view("v", S.v);
+            std::printf("]");
+        }
+        std::printf(" consts=");
+        for (size_t O : constsOf(L)) {
+            const size_t End = *std::upper_bound(Starts.begin(), Starts.end(), O);
+            std::printf("%zu+%zu:%016" PRIx64 ",", O, End - O, hashFloats(P.weights, O, End));
+        }
+        std::printf("\n");
+    }
+    std::printf("outputs");
+    view("policy", P.policy);
+    view("value", P.value);
+    view("draw", P.draw);
+    std::printf("\n");
+}
+
+} // namespace
+
+int main(int Argc, char** Argv) {
+    int Planes = 86;
+    for (int A = 1; A < Argc; ++A) {
+        if (!std::strcmp(Argv[A], "--planes") && A + 1 < Argc) {
+            Planes = std::atoi(Argv[++A]);
+            continue;
+        }
+        const char* Slash = std::strrchr(Argv[A], '/');
+        std::printf("== %s planes=%d\n", Slash ? Slash + 1 : Argv[A], Planes);
+        std::ifstream F(Argv[A], std::ios::binary);
+        if (!F) {
+            std::printf("ERROR cannot read the file\n");
+            continue;
+        }
+        const std::string Data((std::istreambuf_iterator<char>(F)), std::istreambuf_iterator<char>());
+        GraphPlan P;
+        std::string Err;
+        if (buildPlan(Data.data(), Data.size(), Planes, &P, &Err)) dump(P);
+        else std::printf("ERROR %s\n", Err.c_str());
+    }
+    return 0;
+}

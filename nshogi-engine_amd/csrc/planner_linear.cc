@@ -1,0 +1,221 @@
+// planner_linear.cc -- the planner: Conv / Gemm / MatMul with their epilogue.
+#include "planner.h"
+
+namespace nsg::graph {
+
+// A Conv's weights, bias and geometry, checked against the input X
+LinearW Planner::convWeights(const Node& N, const Val& X) {
+    LinearW L;
+    const Val& Wt = host(N, 1, "the weight");
+    if (Wt.isInt || Wt.dims.size() != 4) fail(N, "expected a 4-D float weight [Cout,Cin/group,kh,kw]");
+    const int64_t Kh64 = Wt.dims[2], Kw64 = Wt.dims[3];
+    const std::string KStr = std::to_string(Kh64) + "x" + std::to_string(Kw64);
+    for (int64_t S : N.attrInts("strides", {1, 1}))
+        if (S != 1) fail(N, "stride " + std::to_string(S) + ": only stride 1 (the output stays 9x9)");
+    if (Kh64 < 1 || Kw64 < 1 || Kh64 > 9 || Kw64 > 9 || Kh64 % 2 == 0 || Kw64 % 2 == 0)
+        fail(N, "a " + KStr + " kernel: only odd kernel sizes from 1 to 9 each way");
+    const std::vector<int64_t> Dil = N.attrInts("dilations", {1, 1});
+    if (Dil.size() != 2 || Dil[0] < 1 || Dil[1] < 1) fail(N, "two dilations of at least 1 expected");
+    L.KH = (int)Kh64;
+    L.KW = (int)Kw64;
+    L.DH = L.KH == 1 ? 1 : (int)std::min<int64_t>(Dil[0], 64); // a dilation along an axis of one tap means nothing
+    L.DW = L.KW == 1 ? 1 : (int)std::min<int64_t>(Dil[1], 64);
+    const int Hy = L.DH * (L.KH - 1) / 2, Hx = L.DW * (L.KW - 1) / 2;
+    if (Hy > kMaxConvHalo || Hx > kMaxConvHalo)
+        fail(N, "a " + KStr + " kernel at dilation " + std::to_string(Dil[0]) + "x" + std::to_string(Dil[1]) + " reaches " +
+                    std::to_string(std::max(Hy, Hx)) + " squares past the edge: the halo is at most " + std::to_string(kMaxConvHalo));
+    if (N.Attrs.count("auto_pad")) fail(N, "auto_pad: only explicit pads");
+    const std::vector<int64_t> Pads = N.attrInts("pads", {0, 0, 0, 0});
+    if (Pads != std::vector<int64_t>{Hy, Hx, Hy, Hx}) {
+        std::string Ps;
+        for (int64_t P1 : Pads) Ps += (Ps.empty() ? "" : ",") + std::to_string(P1);
+        fail(N, "pads [" + Ps + "] do not keep the 9x9 board: a " + KStr + " kernel at dilation " + std::to_string(L.DH) + "x" +
+                    std::to_string(L.DW) + " needs [" + std::to_string(Hy) + "," + std::to_string(Hx) + "," + std::to_string(Hy) + "," + std::to_string(Hx) + "]");
+    }
+    L.Cout = (int)Wt.dims[0];
+    if (X.flatOfSpatial || !isSpatialDims(X.dims)) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
+    const int64_t Group = N.attrI("group", 1);
+    if (Group == 1) {
+        L.Cin = (int)Wt.dims[1];
+    } else {
+        // depthwise only: group = Cin = Cout, weight [C,1,kh,kw]
+        const int64_t XC = X.dims[1];
+        if (Group != XC)
+            fail(N, "group " + std::to_string(Group) + " on " + std::to_string(XC) + " input channels: only group 1 or a depthwise conv (group = input channels = output channels)");
+        if (Wt.dims[1] != 1) fail(N, "group " + std::to_string(Group) + " with a weight of " + std::to_string(Wt.dims[1]) + " channels per group: a depthwise weight is [C,1,kh,kw]");
+        if (L.Cout != (int)XC)
+            fail(N, "a depthwise conv with channel multiplier " + std::to_string(XC > 0 ? L.Cout / XC : 0) + " (" + std::to_string(XC) + " -> " +
+                        std::to_string(L.Cout) + " channels): only multiplier 1");
+        L.Depthwise = true;
+        L.Cin = (int)XC;
+    }
+    if ((int)X.dims[1] != L.Cin)
+        fail(N, "the weight expects " + std::to_string(L.Cin) + " input channels, '" + N.In[0] + "' has " + std::to_string(X.dims[1]));
+    L.CinW = L.Depthwise ? 1 : L.Cin;
+    if (Wt.f.size() != (size_t)L.Cout * L.CinW * L.KH * L.KW) fail(N, "the weight's data does not match its shape");
+    L.W.assign(Wt.f.begin(), Wt.f.end());
+    L.Bias.assign((size_t)L.Cout, 0.0);
+    if (has(N, 2)) {
+        const Val& B = host(N, 2, "the bias");
+        if ((int)B.count() != L.Cout) fail(N, "bias length does not match the output channels");
+        for (int C = 0; C < L.Cout; ++C) L.Bias[(size_t)C] = B.at((size_t)C);
+    }
+    return L;
+}
+
+// A Gemm's or MatMul's weights [Cout][Cin] and bias, checked against the input X (Tok: a token tensor)
+LinearW Planner::denseWeights(const Node& N, const Val& X, bool Tok) {
+    LinearW L;
+    const Val& Wt = host(N, 1, "the weight");
+    if (Wt.isInt || Wt.dims.size() != 2) fail(N, "expected a 2-D float weight");
+    bool TransB = false;
+    if (N.Op == "Gemm") {
+        if (N.attrF("alpha", 1.0) != 1.0 || N.attrF("beta", 1.0) != 1.0 || N.attrI("transA", 0) != 0)
+            fail(N, "Gemm with alpha = beta = 1, transA = 0 only");
+        TransB = N.attrI("transB", 0) != 0;
+    }
+    const int Cout = L.Cout = (int)(TransB ? Wt.dims[0] : Wt.dims[1]);
+    const int Cin = L.Cin = L.CinW = (int)(TransB ? Wt.dims[1] : Wt.dims[0]);
+    const int XC = Tok ? (int)X.dims[2] : X.flatOfSpatial ? X.v.C * 81 : flatC(X.dims);
+    if (X.dims.size() != 2 && !X.flatOfSpatial && !Tok) fail(N, "input " + dimsStr(X.dims) + " is not 2-D [N,K]");
+    if (XC != Cin) fail(N, "the weight expects K = " + std::to_string(Cin) + ", '" + N.In[0] + "' has " + std::to_string(XC));
+    L.W.assign((size_t)Cout * Cin, 0.0);
+    for (int O = 0; O < Cout; ++O)
+        for (int I = 0; I < Cin; ++I)
+            L.W[(size_t)O * Cin + I] = TransB ? Wt.f[(size_t)O * Cin + I] : Wt.f[(size_t)I * Cout + O];
+    L.Bias.assign((size_t)Cout, 0.0);
+    if (N.Op == "Gemm" && has(N, 2)) {
+        const Val& B = host(N, 2, "the bias");
+        if ((int)B.count() != Cout && B.count() != 1) fail(N, "bias length does not match");
+        for (int C = 0; C < Cout; ++C) L.Bias[(size_t)C] = B.at(B.count() == 1 ? 0 : (size_t)C);
+    }
+    return L;
+}
+
+// The epilogue behind node N, absorbed while each tensor has one consumer:
+//   [BatchNorm | constant per-channel Add]*  [+ runtime residual]  [activation]
+// BatchNorm and the constant Adds fold into Lw's weights and bias in double.
+Planner::Epilogue Planner::foldEpilogue(const Node& N, size_t Index, const std::vector<int64_t>& Dims, int ChanAxis, int OutForm,
+                                        LinearW* Lw) {
+    const int Cout = Lw->Cout;
+    const size_t PerOut = (size_t)Lw->CinW * Lw->taps();
+    Epilogue E;
+    E.name = N.Name;
+    E.out = N.Out[0];
+    std::string& Cur = E.out;
+    size_t At = Index;
+    while (absorbable(Cur)) {
+        const Node* C = onlyConsumer(Cur, At);
+        if (!C) break;
+        if (C->Op == "BatchNormalization" && E.res.empty() && E.act == kActNone && C->In.size() >= 5 && C->In[0] == Cur) {
+            bool Const = true;
+            for (size_t S = 1; S < 5; ++S) Const = Const && Vals.count(C->In[S]) && !Vals.at(C->In[S]).runtime && Vals.at(C->In[S]).count() == (size_t)Cout;
+            if (!Const) break;
+            for (int O = 0; O < Cout; ++O) {
+                const BnChannel B = bnChannel(*C, (size_t)O);
+                for (size_t J = (size_t)O * PerOut; J < (size_t)(O + 1) * PerOut; ++J) Lw->W[J] *= B.scale;
+                Lw->Bias[(size_t)O] = (Lw->Bias[(size_t)O] - B.mean) * B.scale + B.beta;
+            }
+        } else if (C->Op == "Add" && C->In.size() == 2) {
+            const std::string& Other = C->In[0] == Cur ? C->In[1] : C->In[0];
+            auto It = Vals.find(Other);
+            if (It == Vals.end() || Other == Cur) break;
+            const Val& O = It->second;
+            if (!O.runtime) { // a per-channel constant: the bias
+                if (!E.res.empty() || E.act != kActNone) break;
+                std::vector<int64_t> BD;
+                if (!broadcast(Dims, O.dims, &BD) || BD != Dims) break;
+                const std::vector<int> Ax = variesAlong(O.dims, Dims.size());
+                if (!(Ax.empty() || (Ax.size() == 1 && Ax[0] == ChanAxis))) break;
+                for (int Ch = 0; Ch < Cout; ++Ch) Lw->Bias[(size_t)Ch] += O.at(Ax.empty() ? 0 : (size_t)Ch);
+            } else {
+                if (!E.res.empty() || E.act != kActNone || O.flatOfSpatial || O.dims != Dims || O.form != OutForm) break;
+                E.res = Other;
+            }
+        } else if (E.act == kActNone && !C->In.empty() && C->In[0] == Cur && nodeAct(*C) != kActNone) {
+            E.act = nodeAct(*C);
+        } else {
+            break;
+        }
+        E.name += "+" + C->Name;
+        Skip[indexOf(C)] = true;
+        At = indexOf(C);
+        Cur = C->Out[0];
+        if (E.act != kActNone) break;
+    }
+    return E;
+}
+
+// The conv kernel's weights [tile][chunk][tap][16][64] and bias [tiles * 64]: f32 of the folded doubles
+static void packDense(const LinearW& L, int Chunks, int Tiles, std::vector<float>* Pk, std::vector<float>* Bf) {
+    const int Taps = L.taps();
+    Pk->assign((size_t)Tiles * Chunks * Taps * kChunk * kCoutTile, 0.f);
+    for (int T = 0; T < Tiles; ++T)
+        for (int Ch = 0; Ch < Chunks; ++Ch)
+            for (int Tp = 0; Tp < Taps; ++Tp)
+                for (int Kk = 0; Kk < kChunk; ++Kk)
+                    for (int Nn = 0; Nn < kCoutTile; ++Nn) {
+                        const int O = T * kCoutTile + Nn, I = Ch * kChunk + Kk;
+                        if (O >= L.Cout || I >= L.Cin) continue;
+                        (*Pk)[((((size_t)T * Chunks + Ch) * Taps + Tp) * kChunk + Kk) * kCoutTile + Nn] =
+                            (float)L.W[((size_t)O * L.Cin + I) * Taps + Tp];
+                    }
+    Bf->assign((size_t)Tiles * kCoutTile, 0.f);
+    for (int O = 0; O < L.Cout; ++O) (*Bf)[(size_t)O] = (float)L.Bias[(size_t)O];
+}
+
+// The depthwise kernel's per-channel taps [chunk][tap][16] and bias [chunks * 16]
+static void packDepthwise(const LinearW& L, int Chunks, std::vector<float>* Pk, std::vector<float>* Bf) {
+    const int Taps = L.taps();
+    Pk->assign((size_t)Chunks * Taps * kChunk, 0.f);
+    for (int C = 0; C < L.Cout; ++C)
+        for (int Tp = 0; Tp < Taps; ++Tp)
+            (*Pk)[((size_t)(C / kChunk) * Taps + Tp) * kChunk + C % kChunk] = (float)L.W[(size_t)C * Taps + Tp];
+    Bf->assign((size_t)Chunks * kChunk, 0.f);
+    for (int O = 0; O < L.Cout; ++O) (*Bf)[(size_t)O] = (float)L.Bias[(size_t)O];
+}
+
+// ---- Conv / Gemm / MatMul with their epilogue: one kLaunchConv -------------------------------------------------------
+void Planner::linear(const Node& N, size_t Index) {
+    const Val& X = get(N, 0);
+    if (!X.runtime) fail(N, "the data input is a constant");
+    const bool Dense = N.Op != "Conv";
+    const bool Tok = X.form == kFormToken; // a Linear over tokens: the 1x1 form of the conv, rows = (board, square)
+    if (Tok && N.Op != "MatMul") fail(N, "a token tensor " + dimsStr(X.dims) + " feeds MatMul, not " + N.Op);
+    LinearW Lw = Dense ? denseWeights(N, X, Tok) : convWeights(N, X);
+    const int Cout = Lw.Cout;
+    const std::vector<int64_t> Dims = Tok ? std::vector<int64_t>{kBatch, 81, Cout}
+                                          : Dense ? std::vector<int64_t>{kBatch, Cout} : std::vector<int64_t>{kBatch, Cout, 9, 9};
+    const int OutForm = Tok ? kFormToken : kFormPlain;
+    const Epilogue E = foldEpilogue(N, Index, Dims, Tok ? 2 : 1, OutForm, &Lw);
+    Launch L;
+    L.kind = kLaunchConv;
+    L.name = E.name;
+    L.dense = Dense && !Tok;
+    L.depthwise = Lw.Depthwise;
+    L.taps = Lw.taps();
+    L.kh = Lw.KH;
+    L.kw = Lw.KW;
+    L.dh = Lw.DH;
+    L.dw = Lw.DW;
+    L.in = plain(N.In[0], N.Name + " (input copy)");
+    L.cinPad = roundUp(Lw.Cin, kChunk);
+    L.coutTiles = Lw.Depthwise ? 0 : (Cout + kCoutTile - 1) / kCoutTile;
+    L.act = E.act;
+    L.res.buf = kNoRes;
+    if (!E.res.empty()) L.res = ready(E.res).v;
+    std::vector<float> Pk, Bf;
+    if (Lw.Depthwise) packDepthwise(Lw, L.cinPad / kChunk, &Pk, &Bf);
+    else packDense(Lw, L.cinPad / kChunk, L.coutTiles, &Pk, &Bf);
+    L.wOff = addConst(Pk);
+    L.biasOff = addConst(Bf);
+    L.out = freshView(Cout, !L.dense);
+    P.flopsPerPosition += 2.0 * (L.dense ? 1 : 81) * L.taps * (double)Lw.CinW * Cout;
+    Val V = runtimeVal(N, Dims, OutForm);
+    V.v = L.out;
+    V.producer = N.Name;
+    emit(L);
+    Vals[E.out] = V;
+}
+
+} // namespace nsg::graph

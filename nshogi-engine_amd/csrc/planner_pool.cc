@@ -1,0 +1,98 @@
+// planner_pool.cc -- the planner: pooling and the reductions over the board.
+#include "planner.h"
+
+namespace nsg::graph {
+
+// ---- MaxPool / AveragePool that keep the board: one kLaunchPool.  A MaxPool whose window is the whole board (what the
+// exporter writes for adaptive_max_pool2d(x, 1)) is the global max: one kLaunchMax.
+void Planner::pool(const Node& N) {
+    const Val& X = get(N, 0);
+    const bool Max = N.Op == "MaxPool";
+    if (X.form != kFormPlain || X.flatOfSpatial || !isSpatialDims(X.dims))
+        fail(N, "input " + dimsStr(X.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)X.v.C * 81} : X.dims) +
+                    " is not [N,C,9,9]: pooling runs on a spatial tensor only");
+    const int C = (int)X.dims[1];
+    const std::vector<int64_t> Ks = N.attrInts("kernel_shape", {});
+    if (Ks.size() != 2) fail(N, "a kernel_shape of two sizes expected");
+    const std::string KStr = std::to_string(Ks[0]) + "x" + std::to_string(Ks[1]);
+    if (N.Out.size() > 1 && !N.Out[1].empty() && Uses.count(N.Out[1]))
+        fail(N, "the Indices output '" + N.Out[1] + "' is used: only the pooled values are computed");
+    const std::vector<int64_t> Dil = N.attrInts("dilations", {1, 1});
+    if (Dil.size() != 2 || Dil[0] < 1 || Dil[1] < 1) fail(N, "two dilations of at least 1 expected");
+    const std::vector<int64_t> Pads = N.attrInts("pads", {0, 0, 0, 0});
+    const bool Ceil = N.attrI("ceil_mode", 0) != 0, AutoPad = N.Attrs.count("auto_pad") != 0;
+    Launch L;
+    L.name = N.Name;
+    if (Max && Ks == std::vector<int64_t>{9, 9} && Pads == std::vector<int64_t>{0, 0, 0, 0} && Dil == std::vector<int64_t>{1, 1} &&
+        !Ceil && !AutoPad) { // one window: the strides do not matter
+        L.kind = kLaunchMax;
+        L.in = ready(N.In[0]).v;
+        L.out = freshView(C, false);
+        Val V = runtimeVal(N, {kBatch, C, 1, 1});
+        V.v = L.out;
+        emit(L);
+        Vals[N.Out[0]] = V;
+        return;
+    }
+    for (int64_t S : N.attrInts("strides", {1, 1}))
+        if (S != 1) fail(N, "stride " + std::to_string(S) + ": only stride 1 (the output stays 9x9)");
+    if (Ks[0] < 1 || Ks[1] < 1 || Ks[0] > 9 || Ks[1] > 9 || Ks[0] % 2 == 0 || Ks[1] % 2 == 0)
+        fail(N, "a " + KStr + " kernel: only odd kernel sizes from 1 to 9 each way");
+    if (Ceil) fail(N, "ceil_mode 1: only ceil_mode 0");
+    if (!Max && Dil != std::vector<int64_t>{1, 1}) fail(N, "a dilated AveragePool: dilations on MaxPool only");
+    const int KH = (int)Ks[0], KW = (int)Ks[1];
+    const int DH = KH == 1 ? 1 : (int)std::min<int64_t>(Dil[0], 64), DW = KW == 1 ? 1 : (int)std::min<int64_t>(Dil[1], 64);
+    const int Hy = DH * (KH - 1) / 2, Hx = DW * (KW - 1) / 2;
+    if (Hy > kMaxConvHalo || Hx > kMaxConvHalo)
+        fail(N, "a " + KStr + " kernel at dilation " + std::to_string(Dil[0]) + "x" + std::to_string(Dil[1]) + " reaches " +
+                    std::to_string(std::max(Hy, Hx)) + " squares past the edge: the halo is at most " + std::to_string(kMaxConvHalo));
+    if (AutoPad) fail(N, "auto_pad: only explicit pads");
+    if (Pads != std::vector<int64_t>{Hy, Hx, Hy, Hx}) {
+        std::string Ps;
+        for (int64_t P1 : Pads) Ps += (Ps.empty() ? "" : ",") + std::to_string(P1);
+        fail(N, "pads [" + Ps + "] do not keep the 9x9 board: a " + KStr + " kernel at dilation " + std::to_string(DH) + "x" +
+                    std::to_string(DW) + " needs [" + std::to_string(Hy) + "," + std::to_string(Hx) + "," + std::to_string(Hy) + "," + std::to_string(Hx) + "]");
+    }
+    L.kind = kLaunchPool;
+    L.kh = KH;
+    L.kw = KW;
+    L.dh = DH;
+    L.dw = DW;
+    L.poolMode = Max ? kPoolMax : N.attrI("count_include_pad", 0) != 0 ? kPoolAvgInclude : kPoolAvgExclude;
+    L.in = ready(N.In[0]).v; // a view at any channel offset: the kernel reads an unaligned one with scalar loads
+    L.out = freshView(C, true);
+    Val V = runtimeVal(N, X.dims);
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+}
+
+// ---- GlobalAveragePool / ReduceMean / GlobalMaxPool / ReduceMax over the squares: one kLaunchMean or kLaunchMax
+void Planner::reduceSquares(const Node& N) {
+    const std::string& Op = N.Op;
+    const Val& X = get(N, 0);
+    const bool Reduce = Op == "ReduceMean" || Op == "ReduceMax";
+    const bool Tok = X.form == kFormToken && Reduce;
+    if (!Tok && (X.flatOfSpatial || !isSpatialDims(X.dims))) fail(N, "input " + dimsStr(X.dims) + " is not [N,C,9,9]");
+    bool Keep = true;
+    if (Reduce) {
+        std::vector<int64_t> Axes = axes(N, Tok ? 3 : 4);
+        std::sort(Axes.begin(), Axes.end());
+        if (Tok ? Axes != std::vector<int64_t>{1} : Axes != std::vector<int64_t>{2, 3})
+            fail(N, Op + " over the squares only: axes {2,3} of [N,C,9,9], axis 1 of a token tensor");
+        Keep = N.attrI("keepdims", 1) != 0;
+        if (Tok && Keep) fail(N, Op + " of a token tensor with keepdims = 0 only");
+    }
+    const int C = Tok ? (int)X.dims[2] : (int)X.dims[1];
+    Launch L;
+    L.kind = Op == "GlobalMaxPool" || Op == "ReduceMax" ? kLaunchMax : kLaunchMean;
+    L.name = N.Name;
+    L.in = ready(N.In[0]).v;
+    L.out = freshView(C, false);
+    Val V = runtimeVal(N, Keep ? std::vector<int64_t>{kBatch, C, 1, 1} : std::vector<int64_t>{kBatch, C});
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+}
+
+} // namespace nsg::graph

@@ -1,0 +1,472 @@
+// planner_views.cc -- the planner: views, channel ops and the attention pattern.
+#include "planner.h"
+
+namespace nsg::graph {
+
+// The dims a Reshape of a tensor of dims SD produces (batch symbolic).
+std::vector<int64_t> Planner::reshapeTarget(const Node& N, const std::vector<int64_t>& SD) {
+    int64_t Rest = 1;
+    for (size_t J = 1; J < SD.size(); ++J) Rest *= SD[J];
+    std::vector<int64_t> ND;
+    const std::vector<int64_t> Sh = ints(N, 1, "the target shape");
+    int64_t Known = 1;
+    int Infer = -1;
+    ND.assign(Sh.size(), 0);
+    for (size_t J = 0; J < Sh.size(); ++J) {
+        int64_t V = Sh[J];
+        if (V == 0 && J < SD.size()) V = SD[J];
+        if (V == -1) { Infer = (int)J; continue; }
+        ND[J] = V;
+        if (V != kBatch) Known *= V;
+    }
+    const bool HasBatch = std::count(ND.begin(), ND.end(), kBatch) == 1;
+    if (Infer >= 0) {
+        if (HasBatch) {
+            if (Known <= 0 || Rest % Known) fail(N, "cannot infer the -1 dimension");
+            ND[(size_t)Infer] = Rest / Known;
+        } else {
+            if (Known != Rest) fail(N, "reshape would mix boards");
+            ND[(size_t)Infer] = kBatch;
+        }
+    }
+    if (ND.empty() || ND[0] != kBatch) fail(N, "the target shape " + dimsStr(ND) + " does not keep the batch first");
+    int64_t NR = 1;
+    for (size_t J = 1; J < ND.size(); ++J) NR *= ND[J];
+    if (NR != Rest) fail(N, "element count changes: " + dimsStr(SD) + " -> " + dimsStr(ND));
+    return ND;
+}
+
+// ---- views between [N,C,9,9], [N,C,81], tokens [N,81,C] and the attention pattern's 4-D shapes: no launch, except
+// the Reshape that closes the attention pattern.  Returns false when N is not such a view (the caller goes on).
+bool Planner::formView(const Node& N) {
+    const std::string& Op = N.Op;
+    if (Op != "Transpose" && Op != "Reshape" && Op != "Flatten" && Op != "Identity") return false;
+    const Val& X0 = get(N, 0);
+    if (!X0.runtime) return false;
+    if (Op == "Identity") {
+        if (X0.form == kFormPlain) return false;
+        if (X0.form >= kFormChan3) interior(N, 0);
+        Val V = ready(N.In[0]);
+        Vals[N.Out[0]] = V;
+        return true;
+    }
+    if (X0.normG > 0 && Op != "Reshape")
+        fail(N, "'" + N.In[0] + "' " + dimsStr(X0.dims) + " is the normalised tensor of a GroupNorm pattern: only the Reshape back to [N,C,9,9] reads it (DESIGN.md section 13.3)");
+    const std::vector<int64_t> Perm = N.attrInts("perm", {});
+    auto set = [&](Val V, int Form, std::vector<int64_t> Dims) {
+        V.form = Form;
+        V.dims = std::move(Dims);
+        V.producer = N.Name;
+        V.chain += (V.chain.empty() ? "" : "+") + N.Name;
+        Vals[N.Out[0]] = V;
+        return true;
+    };
+    if (Op == "Transpose") {
+        const int F = X0.form;
+        // the channel-last view of a spatial tensor and the way back: the same rows, no launch
+        if (F == kFormPlain && !X0.flatOfSpatial && isSpatialDims(X0.dims) && Perm == std::vector<int64_t>{0, 2, 3, 1}) {
+            Val V = ready(N.In[0]);
+            V.chain.clear();
+            return set(V, kFormChanLast, {kBatch, 9, 9, X0.dims[1]});
+        }
+        if (F == kFormChanLast) {
+            if (Perm != std::vector<int64_t>{0, 3, 1, 2})
+                fail(N, "Transpose of the channel-last view " + dimsStr(X0.dims) + " with perm " + dimsStr(Perm) + ": only [0,3,1,2], back to [N,C,9,9]");
+            Val V = X0;
+            V.chain.clear();
+            return set(V, kFormPlain, {kBatch, X0.dims[3], 9, 9});
+        }
+        if (F == kFormGroup3) fail(N, "Transpose of " + dimsStr(X0.dims) + ": the groups [N,G,M] of a GroupNorm pattern feed an InstanceNormalization only");
+        if (F == kFormPlain) return false; // refused by the caller, with the shapes
+        if (F >= kFormChan3) interior(N, 0);
+        const Val X = F == kFormToken ? ready(N.In[0]) : X0;
+        const std::vector<int64_t>& D = X.dims;
+        if ((F == kFormToken || F == kFormChan3) && Perm == std::vector<int64_t>{0, 2, 1}) {
+            Val V = X;
+            V.chain.clear();
+            return set(V, F == kFormToken ? kFormChan3 : kFormToken, {kBatch, D[2], D[1]});
+        }
+        if (F == kFormTok4 && Perm == std::vector<int64_t>{0, 2, 1, 3}) return set(X, kFormHeads, {kBatch, D[2], 81, D[3]});
+        if (F == kFormTok4 && Perm == std::vector<int64_t>{0, 2, 3, 1}) return set(X, kFormHeadsT, {kBatch, D[2], D[3], 81});
+        if (F == kFormHeads && Perm == std::vector<int64_t>{0, 1, 3, 2}) return set(X, kFormHeadsT, {kBatch, D[1], D[3], 81});
+        if (F == kFormHeadOut && Perm == std::vector<int64_t>{0, 2, 1, 3}) return set(X, kFormTokOut4, {kBatch, 81, D[1], D[3]});
+        fail(N, "Transpose of " + dimsStr(D) + " with perm " + dimsStr(Perm) + " is outside the token-view and attention patterns (DESIGN.md section 13.3)");
+    }
+    // Reshape / Flatten
+    const int F = X0.form;
+    const bool PlainSpatial = F == kFormPlain && !X0.flatOfSpatial && isSpatialDims(X0.dims);
+    if (F == kFormPlain && !PlainSpatial) return false;
+    if (PlainSpatial) {
+        // only Reshape to [N,C,81] is taken here (torch's flatten(2)); every other view is the existing code's.  ONNX's
+        // own Flatten with axis 2 gives [N*C,81], which mixes boards, and is refused there.
+        if (Op != "Reshape") return false;
+        const Val& ShV = get(N, 1);
+        if (ShV.runtime || ShV.count() != 3) return false;
+        const std::vector<int64_t> ND = reshapeTarget(N, X0.dims);
+        if (ND != std::vector<int64_t>{kBatch, X0.dims[1], 81}) {
+            // [N,G,M] with G M = C 81 in front of an InstanceNormalization: the groups of a GroupNorm
+            if (ND[1] <= 0 || ND[2] <= 0 || ND[1] * ND[2] != X0.dims[1] * 81) return false;
+            bool Norm = false;
+            for (size_t K = indexOf(&N) + 1; K < Nodes.size(); ++K)
+                Norm = Norm || (!Skip[K] && Nodes[K].Op == "InstanceNormalization" && !Nodes[K].In.empty() && Nodes[K].In[0] == N.Out[0]);
+            if (!Norm) return false;
+            if (X0.dims[1] % ND[1] != 0)
+                fail(N, "a GroupNorm of " + std::to_string(ND[1]) + " groups over " + std::to_string(X0.dims[1]) + " channels: the group count does not divide the channels");
+            Val V = ready(N.In[0]);
+            V.chain.clear();
+            return set(V, kFormGroup3, ND);
+        }
+        Val V = ready(N.In[0]);
+        V.chain.clear();
+        return set(V, kFormChan3, ND);
+    }
+    if (Op == "Flatten" && !(F == kFormChan3 && N.attrI("axis", 1) == 1))
+        fail(N, "Flatten of " + dimsStr(X0.dims) + " is outside the token-view patterns");
+    if (X0.normG > 0) { // the Reshape that closes the GroupNorm pattern: one launch, with what follows it
+        const std::vector<int64_t> Back = reshapeTarget(N, X0.dims);
+        if (Back != std::vector<int64_t>{kBatch, (int64_t)X0.v.C, 9, 9})
+            fail(N, "the normalised groups " + dimsStr(X0.dims) + " are reshaped to " + dimsStr(Back) + ", not back to [N," + std::to_string(X0.v.C) + ",9,9]");
+        groupNorm(N, indexOf(&N), X0.v, X0.v.C, X0.normG, X0.normA, X0.normB, X0.normEps, X0.chain + "+" + N.Name);
+        return true;
+    }
+    if (F == kFormGroup3) fail(N, "Reshape of " + dimsStr(X0.dims) + ": the groups [N,G,M] of a GroupNorm pattern feed an InstanceNormalization only");
+    if (F == kFormChanLast) fail(N, "Reshape of the channel-last view " + dimsStr(X0.dims) + ": only a LayerNorm over the channels and Transpose [0,3,1,2] read it");
+    if (F >= kFormChan3) interior(N, 0);
+    const std::vector<int64_t> ND = Op == "Flatten" ? std::vector<int64_t>{kBatch, X0.dims[1] * 81} : reshapeTarget(N, X0.dims);
+    if (F == kFormChan3) { // the way back: [N,C,81] -> [N,C,9,9] or the flattened [N,C*81]
+        Val V = X0;
+        V.form = kFormPlain;
+        V.producer = N.Name;
+        V.chain.clear();
+        if (isSpatialDims(ND) && ND[1] == X0.dims[1]) V.dims = ND;
+        else if (ND == std::vector<int64_t>{kBatch, X0.dims[1] * 81}) { V.dims = {kBatch, X0.dims[1], 9, 9}; V.flatOfSpatial = true; }
+        else fail(N, "a [N,C,81] tensor can become [N,C,9,9] or [N,C*81], not " + dimsStr(ND));
+        Vals[N.Out[0]] = V;
+        return true;
+    }
+    if (F == kFormToken) {
+        if (ND == X0.dims) { Val V = ready(N.In[0]); V.producer = N.Name; Vals[N.Out[0]] = V; return true; }
+        const int C = (int)X0.dims[2];
+        if (ND.size() != 4 || ND[1] != 81 || ND[2] <= 0 || ND[3] <= 0 || ND[2] * ND[3] != C)
+            fail(N, "a token tensor " + dimsStr(X0.dims) + " can be split into heads [N,81,H,d], not reshaped to " + dimsStr(ND));
+        const int64_t Hd = ND[3];
+        if (Hd % 4 != 0 || Hd > kMaxHeadDim)
+            fail(N, "head dimension " + std::to_string(Hd) + ": the attention kernel takes multiples of 4 up to " + std::to_string(kMaxHeadDim));
+        const Val V = headsSource(N, X0);
+        if (V.v.offset % 4 != 0) fail(N, "'" + N.In[0] + "' starts at channel " + std::to_string(V.v.offset) + " of its row: the attention kernel reads views at multiples of 4");
+        return set(V, kFormTok4, ND);
+    }
+    if (F == kFormTokOut4) { // the Reshape that closes the pattern: one launch
+        const int64_t H = X0.dims[2], Hd = X0.dims[3];
+        if (ND != std::vector<int64_t>{kBatch, 81, H * Hd})
+            fail(N, "the attention output " + dimsStr(X0.dims) + " is reshaped to " + dimsStr(ND) + ", not to [N,81,H*d]");
+        attentionLaunch(N, X0, ND);
+        return true;
+    }
+    fail(N, "Reshape of " + dimsStr(X0.dims) + " is outside the token-view and attention patterns (DESIGN.md section 13.3)");
+}
+
+// The token tensor a Reshape splits into heads.  q * scale (or k * scale) right before the split: an open group of one
+// scalar Mul / Div is folded into the scale and never launched.
+Val Planner::headsSource(const Node& N, const Val& X0) {
+    if (X0.group >= 0 && absorbable(N.In[0])) {
+        const Group& Gr = Groups[(size_t)X0.group];
+        if (Gr.open && Gr.srcs.size() == 2 && Gr.code.size() == 3 && Gr.code[0].op == kEltLoad && Gr.code[1].op == kEltLoad &&
+            (Gr.code[2].op == kEltMul || Gr.code[2].op == kEltDiv)) {
+            const int A = Gr.code[2].a, B = Gr.code[2].b; // registers loaded by code[0] and code[1]
+            const EltSrc& SA = Gr.srcs[Gr.code[A == Gr.code[0].dst ? 0 : 1].a];
+            const EltSrc& SB = Gr.srcs[Gr.code[B == Gr.code[0].dst ? 0 : 1].a];
+            const bool Mul = Gr.code[2].op == kEltMul;
+            const EltSrc* Rt = SA.mode == kSrcSame ? &SA : (Mul && SB.mode == kSrcSame) ? &SB : nullptr;
+            const EltSrc* Cs = Rt == &SA ? &SB : &SA;
+            if (A != B && Rt && Cs->mode == kSrcScalar && Gr.outReg == Gr.code[2].dst) {
+                Val V = X0;
+                V.group = -1;
+                V.v = Rt->v;
+                V.scale = Mul ? (double)Cs->scalar : 1.0 / (double)Cs->scalar;
+                V.chain = Gr.name;
+                Groups[(size_t)X0.group].open = false;
+                return V;
+            }
+        }
+    }
+    Val V = ready(N.In[0]);
+    V.scale = 1.0;
+    V.chain.clear();
+    return V;
+}
+
+// The Reshape of [N,81,H,d] to ND = [N,81,H*d] that closes the attention pattern: its one launch
+void Planner::attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND) {
+    const int64_t H = X0.dims[2], Hd = X0.dims[3];
+    Launch L;
+    L.kind = kLaunchAttention;
+    L.name = X0.chain + "+" + N.Name;
+    L.in = X0.attQ;
+    L.attK = X0.attK;
+    L.attV = X0.attV;
+    L.heads = (int)H;
+    L.headDim = (int)Hd;
+    L.scale = (float)X0.scale;
+    L.hasBias = !X0.bias.empty();
+    if (L.hasBias) {
+        std::vector<float> Bf(X0.bias.begin(), X0.bias.end());
+        L.biasOff = addConst(Bf);
+    }
+    L.out = freshView((int)(H * Hd), true);
+    P.flopsPerPosition += 2.0 * (2.0 * 81 * 81 * (double)Hd) * (double)H; // q k^T and probs x v
+    Val V = runtimeVal(N, ND, kFormToken);
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+}
+
+// ---- the attention pattern's arithmetic: q k^T, the scalar factors, the constant bias, the Softmax, probs x v.
+// Nothing is launched here: the state travels in the Val until the closing Reshape (formView).
+bool Planner::attentionOp(const Node& N) {
+    const std::string& Op = N.Op;
+    const bool Binary = Op == "MatMul" || Op == "Mul" || Op == "Div" || Op == "Add";
+    if (!Binary && Op != "Softmax") return false;
+    const Val& A = get(N, 0);
+    const Val* B = Binary ? &get(N, 1) : nullptr;
+    const int FA = A.runtime ? A.form : kFormPlain, FB = B && B->runtime ? B->form : kFormPlain;
+    if (!isAttForm(FA) && !isAttForm(FB)) return false;
+    auto put = [&](Val V, int Form, std::vector<int64_t> Dims) {
+        V.form = Form;
+        V.dims = std::move(Dims);
+        V.producer = N.Name;
+        V.chain += "+" + N.Name;
+        Vals[N.Out[0]] = V;
+        return true;
+    };
+    if (Op == "Softmax") {
+        if (FA != kFormScores) fail(N, "Softmax on " + dimsStr(A.dims) + ": only the softmax over the keys of [N,H,81,81] attention scores is supported");
+        int64_t Axis = N.attrI("axis", -1);
+        if (Axis < 0) Axis += 4;
+        if (Axis != 3) fail(N, "Softmax over axis " + std::to_string(N.attrI("axis", -1)) + " of the attention scores: the keys (axis -1) only");
+        interior(N, 0);
+        return put(A, kFormProbs, A.dims);
+    }
+    if (Op == "MatMul") {
+        if (FA == kFormHeads && FB == kFormHeadsT) {
+            interior(N, 0);
+            interior(N, 1);
+            if (A.dims[1] != B->dims[1] || A.dims[3] != B->dims[2])
+                fail(N, "q " + dimsStr(A.dims) + " and k^T " + dimsStr(B->dims) + " do not agree in heads and head dimension");
+            Val V = A;
+            V.attQ = A.v;
+            V.attK = B->v;
+            V.scale = A.scale * B->scale;
+            V.chain = A.chain + "+" + B->chain;
+            V.bias.clear();
+            return put(V, kFormScores, {kBatch, A.dims[1], 81, 81});
+        }
+        if (FA == kFormProbs && FB == kFormHeads) {
+            interior(N, 0);
+            interior(N, 1);
+            if (B->scale != 1.0) fail(N, "a scalar factor on v is not part of the attention pattern");
+            if (A.dims[1] != B->dims[1]) fail(N, "the attention weights have " + std::to_string(A.dims[1]) + " heads, v has " + std::to_string(B->dims[1]));
+            const int64_t QD = A.attQ.C / A.dims[1];
+            if (QD != B->dims[3]) fail(N, "q and k have head dimension " + std::to_string(QD) + ", v has " + std::to_string(B->dims[3]));
+            Val V = A;
+            V.attV = B->v;
+            V.chain = A.chain + "+" + B->chain;
+            return put(V, kFormHeadOut, {kBatch, A.dims[1], 81, B->dims[3]});
+        }
+        fail(N, "MatMul of " + dimsStr(A.dims) + " and " + dimsStr(B->dims) + " is outside the attention pattern (q k^T, then softmax x v; DESIGN.md section 13.3)");
+    }
+    // Mul / Div / Add with a constant
+    const bool AR = isAttForm(FA);
+    const Val& T = AR ? A : *B;
+    const Val& Cst = AR ? *B : A;
+    if (Cst.runtime) fail(N, "the other operand of " + Op + " on " + dimsStr(T.dims) + " is computed at run time: only constants enter the attention pattern");
+    interior(N, AR ? 0 : 1);
+    if (Op == "Mul" || Op == "Div") {
+        if (Cst.count() != 1) fail(N, "only a scalar constant scales the attention pattern's tensors");
+        if (Op == "Div" && !AR) fail(N, "a constant divided by " + dimsStr(T.dims) + " is outside the attention pattern");
+        if (T.form != kFormTok4 && T.form != kFormHeads && T.form != kFormHeadsT && T.form != kFormScores)
+            fail(N, Op + " on " + dimsStr(T.dims) + " is outside the attention pattern");
+        const double S = Op == "Mul" ? Cst.at(0) : 1.0 / Cst.at(0);
+        Val V = T;
+        V.scale *= S;
+        for (double& Bv : V.bias) Bv *= S;
+        return put(V, T.form, T.dims);
+    }
+    // Add: a constant bias on the scores
+    if (T.form != kFormScores) fail(N, "Add on " + dimsStr(T.dims) + " is outside the attention pattern (a constant bias is added to the scores)");
+    const int64_t H = T.dims[1];
+    std::vector<int64_t> CD = Cst.dims;
+    if (CD.size() == 4 && CD[0] == 1) CD.erase(CD.begin());
+    const bool PerHead = CD == std::vector<int64_t>{H, 81, 81};
+    if (!PerHead && CD != std::vector<int64_t>{81, 81} && CD != std::vector<int64_t>{1, 81, 81})
+        fail(N, "an attention bias of shape " + dimsStr(Cst.dims) + ": [H,81,81], [1,H,81,81] or [81,81] only");
+    Val V = T;
+    if (V.bias.empty()) V.bias.assign((size_t)H * 81 * 81, 0.0);
+    for (size_t J = 0; J < V.bias.size(); ++J) V.bias[J] += Cst.at(PerHead ? J : J % (81 * 81));
+    return put(V, kFormScores, T.dims);
+}
+
+// ---- Flatten / Reshape / Squeeze / Unsqueeze / Identity between [N,C,9,9], its flattened [N,C*81] and the flat shapes:
+// no launch.  An open elementwise group read only here stays open: the reshaped tensor is its new result (a [N,C,9,9]
+// group that becomes [N,C*81] is emitted first: the flattened view reads its buffer).
+void Planner::viewOp(const Node& N) {
+    const std::string& Op = N.Op;
+    bool MoveGroup = Vals.at(N.In[0]).group >= 0 && absorbable(N.In[0]);
+    Val Src = MoveGroup ? Vals.at(N.In[0]) : ready(N.In[0]);
+    const std::vector<int64_t> SD = Src.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)Src.v.C * 81} : Src.dims;
+    int64_t Rest = 1;
+    for (size_t J = 1; J < SD.size(); ++J) Rest *= SD[J];
+    std::vector<int64_t> ND;
+    if (Op == "Identity") ND = SD;
+    else if (Op == "Flatten") {
+        if (N.attrI("axis", 1) != 1) fail(N, "Flatten with axis 1 only");
+        ND = {kBatch, Rest};
+    } else if (Op == "Reshape") {
+        ND = reshapeTarget(N, SD);
+    } else {
+        std::vector<int64_t> Axes = axes(N, SD.size(), Op == "Unsqueeze");
+        ND = SD;
+        if (Op == "Unsqueeze") {
+            std::sort(Axes.begin(), Axes.end());
+            for (int64_t A : Axes) {
+                if (A <= 0 || A > (int64_t)ND.size()) fail(N, "cannot unsqueeze the batch axis");
+                ND.insert(ND.begin() + A, 1);
+            }
+        } else {
+            std::vector<int64_t> Keep;
+            for (size_t J = 0; J < SD.size(); ++J) {
+                bool Drop = Axes.empty() ? (J > 0 && SD[J] == 1) : false;
+                for (int64_t A : Axes) Drop = Drop || A == (int64_t)J;
+                if (Drop && (J == 0 || SD[J] != 1)) fail(N, "squeezes a dimension that is not 1");
+                if (!Drop) Keep.push_back(SD[J]);
+            }
+            ND = Keep;
+        }
+    }
+    int64_t NR = 1;
+    for (size_t J = 1; J < ND.size(); ++J) NR *= ND[J];
+    if (NR != Rest) fail(N, "element count changes: " + dimsStr(SD) + " -> " + dimsStr(ND));
+    const bool SrcSpatial = Src.flatOfSpatial || isSpatialDims(Src.dims);
+    const int64_t SrcC = Src.flatOfSpatial ? (int64_t)Src.v.C : SrcSpatial ? Src.dims[1] : -1;
+    if (MoveGroup && SrcSpatial && !isSpatialDims(ND)) {
+        MoveGroup = false;
+        Src = ready(N.In[0]);
+    }
+    Val V = Src;
+    V.producer = N.Name;
+    V.dims = ND;
+    if (SrcSpatial) {
+        if (isSpatialDims(ND) && ND[1] == SrcC) V.flatOfSpatial = false;
+        else if (ND.size() == 2) V.flatOfSpatial = true;
+        else fail(N, "a [N,C,9,9] tensor can become [N,C*81] or stay [N,C,9,9], not " + dimsStr(ND));
+    } else if (flatC(ND) < 0) {
+        fail(N, "a flat tensor cannot become " + dimsStr(ND));
+    }
+    if (!V.flatOfSpatial && !isSpatialDims(V.dims)) V.dims = ND;
+    if (MoveGroup) Groups[(size_t)V.group].out = N.Out[0];
+    Vals[N.Out[0]] = V;
+}
+
+// ---- Concat along the channels: one kLaunchConcat
+void Planner::concat(const Node& N) {
+    const Val& X = get(N, 0);
+    int64_t Ax = N.attrI("axis", 1);
+    const size_t Rank = X.flatOfSpatial ? 2 : X.dims.size();
+    if (Ax < 0) Ax += (int64_t)Rank;
+    if (Ax != 1) fail(N, "Concat of runtime tensors along axis 1 only");
+    if (N.In.size() > (size_t)kMaxCopySegs) fail(N, "more than " + std::to_string(kMaxCopySegs) + " inputs");
+    Launch L;
+    L.kind = kLaunchConcat;
+    L.name = N.Name;
+    int Total = 0;
+    bool Sp = false;
+    for (size_t J = 0; J < N.In.size(); ++J) {
+        const Val& V = get(N, J);
+        if (!V.runtime) fail(N, "Concat of a runtime tensor and a constant");
+        if (V.form != kFormPlain) fail(N, "Concat of a token tensor " + dimsStr(V.dims));
+        const bool VS = !V.flatOfSpatial && isSpatialDims(V.dims);
+        if (J == 0) Sp = VS;
+        if (VS != Sp) fail(N, "Concat of [N,C,9,9] and flat tensors");
+        if (!Sp && (V.flatOfSpatial ? 2 : V.dims.size()) != Rank) fail(N, "Concat of different ranks");
+        CopySeg S;
+        S.v = V.flatOfSpatial ? plain(N.In[J], N.Name + " (flatten)") : ready(N.In[J]).v;
+        S.dstOff = Total;
+        Total += S.v.C;
+        L.segs.push_back(S);
+    }
+    L.out = freshView(Total, Sp);
+    std::vector<int64_t> ND = Sp ? std::vector<int64_t>{kBatch, Total, 9, 9} : std::vector<int64_t>{kBatch, Total};
+    if (!Sp) for (size_t J = 2; J < Rank; ++J) ND.push_back(1);
+    Val V = runtimeVal(N, ND);
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+}
+
+// ---- Slice along the channels: a view
+void Planner::slice(const Node& N) {
+    const Val Src = get(N, 0).flatOfSpatial ? (plain(N.In[0], N.Name + " (flatten)"), Vals.at(N.In[0])) : ready(N.In[0]);
+    const std::vector<int64_t> St = ints(N, 1, "starts"), En = ints(N, 2, "ends");
+    std::vector<int64_t> Axes = has(N, 3) ? ints(N, 3, "axes") : std::vector<int64_t>();
+    const std::vector<int64_t> Sp = has(N, 4) ? ints(N, 4, "steps") : std::vector<int64_t>(St.size(), 1);
+    if (Axes.empty()) for (size_t J = 0; J < St.size(); ++J) Axes.push_back((int64_t)J);
+    if (St.size() != En.size() || Axes.size() != St.size() || Sp.size() != St.size()) fail(N, "malformed Slice");
+    Val V = Src;
+    V.producer = N.Name;
+    const int64_t ChanAxis = Src.form == kFormToken ? 2 : 1;
+    for (size_t J = 0; J < Axes.size(); ++J) {
+        int64_t A = Axes[J] < 0 ? Axes[J] + (int64_t)Src.dims.size() : Axes[J];
+        if (Sp[J] != 1) fail(N, "Slice with a step other than 1");
+        if (A == ChanAxis) {
+            const int64_t Len = Src.v.C;
+            int64_t S = St[J] < 0 ? St[J] + Len : St[J], E = En[J] < 0 ? En[J] + Len : En[J];
+            S = std::max<int64_t>(0, std::min(S, Len));
+            E = std::max<int64_t>(S, std::min(E, Len));
+            if (E == S) fail(N, "empty slice");
+            V.v.offset += (int)S;
+            V.v.C = (int)(E - S);
+            V.dims[(size_t)ChanAxis] = E - S;
+        } else {
+            const int64_t Dim = A < (int64_t)Src.dims.size() ? Src.dims[(size_t)A] : 1;
+            if (St[J] != 0 || (Dim != kBatch && En[J] < Dim)) fail(N, "Slice along an axis other than the channels");
+        }
+    }
+    Vals[N.Out[0]] = V;
+}
+
+// ---- Split along the channels: every output is a view, like Slice
+void Planner::split(const Node& N) {
+    const Val& X = get(N, 0);
+    if (X.flatOfSpatial) fail(N, "Split of a flattened [N,C*81] view of a spatial tensor");
+    const Val Src = ready(N.In[0]);
+    const int64_t Rank = (int64_t)Src.dims.size(), ChanAxis = Src.form == kFormToken ? 2 : 1;
+    int64_t Axis = N.attrI("axis", 0);
+    if (Axis < 0) Axis += Rank;
+    if (Axis != ChanAxis || Rank < 2) fail(N, "Split of " + dimsStr(Src.dims) + " along axis " + std::to_string(N.attrI("axis", 0)) + ": along the channels only");
+    const int64_t C = Src.v.C;
+    std::vector<int64_t> Sizes = has(N, 1) ? ints(N, 1, "the split sizes") : N.attrInts("split", {});
+    if (Sizes.empty()) {
+        const int64_t Parts = (int64_t)N.Out.size();
+        if (C % Parts) fail(N, std::to_string(C) + " channels do not split into " + std::to_string(Parts) + " equal parts");
+        Sizes.assign((size_t)Parts, C / Parts);
+    }
+    int64_t Sum = 0;
+    for (int64_t S : Sizes) {
+        if (S <= 0) fail(N, "an empty part");
+        Sum += S;
+    }
+    if (Sizes.size() != N.Out.size() || Sum != C)
+        fail(N, "the split sizes do not cover the " + std::to_string(C) + " channels with one part per output");
+    int64_t Off = 0;
+    for (size_t J = 0; J < Sizes.size(); Off += Sizes[J], ++J) {
+        if (N.Out[J].empty()) continue;
+        Val V = Src;
+        V.producer = N.Name;
+        V.v.offset += (int)Off;
+        V.v.C = (int)Sizes[J];
+        V.dims[(size_t)ChanAxis] = Sizes[J];
+        Vals[N.Out[J]] = V;
+    }
+}
+
+} // namespace nsg::graph
