@@ -118,7 +118,14 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    elementary ops, as exported below opset 17); and transformer or conv-plus-attention nets
  *    over the 81 squares as tokens [N,81,C] -- dense layers, LayerNorm, exact
  *    GELU, a learned positional embedding and the multi-head attention
- *    pattern of section 13.3, which runs as one launch per block.  A general graph always runs in
+ *    pattern of section 13.3, which runs as one launch per block.  The scores may take,
+ *    beside a constant bias, one additive bias computed at run time of shape
+ *    [N,H,81,81] or [N,1,81,81] (Lc0's "smolgen" and its like): a token Linear,
+ *    the tokens flattened to [N,81*C] (C a multiple of 16), dense layers, an
+ *    optional [N,H,K] stage with one Linear shared by the heads (K a multiple of
+ *    16), and a Reshape into the scores' shape; the attention still is one
+ *    launch.  A mask input and nn.MultiheadAttention's own export form stay
+ *    refused.  A general graph always runs in
  *    exact fp32, whatever nsg_set_precision asked for.
  * When both refuse, the load fails with NSG_E_FORMAT and a message giving both
  * reasons, the general path's naming the node (the reference's parser

@@ -1,7 +1,7 @@
 // graph_attention.hip -- the general graph path's attention core and LayerNorm, exact f32.
 //
 // graphAttention: a workgroup owns one (board, head).  K is staged in LDS as a 96-row image (rows 81..95 zero), Q is
-// read from global memory straight into the A operand registers, and S = scale * Q K^T (+ bias) goes as six by six
+// read from global memory straight into the A operand registers, and S = scale * Q K^T (+ bias) (+ a run-time bias) goes as six by six
 // 16 x 16 fragments of v_mfma_f32_16x16x4_f32 into a 96 x 96 score image in LDS.  A row softmax in a fixed order
 // follows -- max, expf, sum, divide, one wave per row, keys 81..95 left out of the max and the sum and given
 // probability 0 -- while V is staged over K's image; then O = P V on the MFMA, stored as token rows at channels
@@ -37,12 +37,17 @@ __device__ inline float waveMax(float v) {
 
 // D16: the head dimension d rounded up to 16, in units of 16 (d itself is a multiple of 4, at most 64).
 // LDS: (96 x (16 D16 + 4) + 96 x 100) floats = 64512 bytes at D16 = 4, under the 64 KB static limit.
-template <int D16>
+// RT: a bias computed at run time is added to the scores: rt[board * rtBoard + head * rtHead + query * 81 + key], times
+// rtScale (rtHead 0: one bias for every head).  Per score: acc * scale, then + bias, then + rtScale * rt.  Without RT
+// the arguments are unused and the kernel is the one it was.
+template <int D16, bool RT>
 __global__ __launch_bounds__(kThreads) void graphAttention(const float* __restrict__ q, int qStride, int qOff,
                                                            const float* __restrict__ k, int kStride, int kOff,
                                                            const float* __restrict__ v, int vStride, int vOff,
                                                            const float* __restrict__ bias, float scale,
-                                                           float* __restrict__ out, int outStride, int heads, int d) {
+                                                           float* __restrict__ out, int outStride, int heads, int d,
+                                                           const float* __restrict__ rt, long rtBoard, int rtHead,
+                                                           float rtScale) {
     constexpr int DP = 16 * D16;
     constexpr int KS = DP + 4; // floats per K / V row: 4 x odd, so sixteen rows x four k lanes hit 64 distinct banks
     __shared__ __attribute__((aligned(16))) float sKV[kRows * KS];
@@ -64,6 +69,26 @@ __global__ __launch_bounds__(kThreads) void graphAttention(const float* __restri
 
     // S = scale * Q K^T + bias: 36 fragments, nine per wave; a wave keeps the A operands of its current 16 query rows
     float aQ[4 * D16];
+    // The run-time bias of a fragment, four values per lane, is requested one fragment ahead (the first before the loop),
+    // behind the Q loads of the iteration that issues it, and used after the next fragment's MFMA chain: a whole
+    // iteration -- chain, epilogue and LDS stores -- lies between request and use.  The four loads are unconditional, at
+    // addresses clamped to query 80 and key 80 (inside the (board, head) block, so nothing outside it is read), and a
+    // select puts 0 where the query or the key is past 80; the 16 lanes of a col group read 16 consecutive floats.
+    float rbNext[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* rtBase = nullptr;
+    if constexpr (RT) rtBase = rt + (size_t)b * (size_t)rtBoard + (size_t)h * (size_t)rtHead;
+    auto requestBias = [&](int id) {
+        const int rf = id / 6, cf = id - rf * 6;
+        const int key = cf * 16 + col;
+        const float* rp = rtBase + min(key, 80);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = rf * 16 + 4 * kq + i;
+            const float x = rp[min(r, 80) * 81];
+            rbNext[i] = (r < 81 && key < 81) ? x : 0.f;
+        }
+    };
+    if constexpr (RT) requestBias(wave * 9);
     for (int j = 0; j < 9; ++j) {
         const int id = wave * 9 + j;
         const int rf = id / 6, cf = id - rf * 6;
@@ -73,18 +98,25 @@ __global__ __launch_bounds__(kThreads) void graphAttention(const float* __restri
 #pragma unroll
             for (int k4 = 0; k4 < 4 * D16; ++k4) aQ[k4] = (r < 81 && k4 < dq) ? qr[k4 * 4 + kq] : 0.f;
         }
+        float rb[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (RT) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rb[i] = rbNext[i];
+            if (j + 1 < 9) requestBias(id + 1);
+        }
+        // acc[i] = S[query rf*16 + 4*kq + i][key cf*16 + col]
+        const int key = cf * 16 + col;
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
         const float* kr = sKV + (cf * 16 + col) * KS + kq;
 #pragma unroll
         for (int k4 = 0; k4 < 4 * D16; ++k4)
             if (k4 < dq) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aQ[k4], kr[k4 * 4], acc, 0, 0, 0);
-        // acc[i] = S[query rf*16 + 4*kq + i][key cf*16 + col]
-        const int key = cf * 16 + col;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = rf * 16 + 4 * kq + i;
             float s = acc[i] * scale;
             if (bias && r < 81 && key < 81) s += bias[((size_t)h * 81 + r) * 81 + key];
+            if constexpr (RT) s += rtScale * rb[i]; // rb is 0 past query or key 80
             sS[r * kSStride + key] = s;
         }
     }
@@ -155,17 +187,28 @@ __global__ __launch_bounds__(kThreads) void graphLayerNorm(const float* __restri
 
 } // namespace
 
-hipError_t launchGraphAttention(DevView q, DevView k, DevView v, const float* bias, float scale, float* out,
+hipError_t launchGraphAttention(DevView q, DevView k, DevView v, const float* bias, float scale, RtBias rt, float* out,
                                 int outStride, int heads, int headDim, int boards, hipStream_t stream) {
     const int C = heads * headDim;
     if (boards <= 0 || heads <= 0 || headDim <= 0 || headDim % 4 != 0 || headDim > kMaxHeadDim || outStride < C)
         return hipErrorInvalidValue;
     for (const DevView* x : {&q, &k, &v})
         if (x->C != C || x->offset % 4 != 0 || x->stride % 4 != 0 || x->offset + C > x->stride) return hipErrorInvalidValue;
+    // the last element a workgroup reads, (head heads-1, query 80, key 80), lies inside its board's row
+    if (rt.p && (!(rt.scale > 0.f) || rt.headStride < 0 || rt.boardStride <= 0 || (long)(heads - 1) * rt.headStride + 81 * 81 > rt.boardStride))
+        return hipErrorInvalidValue;
     const dim3 grid((unsigned)boards, (unsigned)heads);
 #define NSG_ATT(D16)                                                                                                    \
-    hipLaunchKernelGGL(graphAttention<D16>, grid, dim3(kThreads), 0, stream, q.p, q.stride, q.offset, k.p, k.stride,   \
-                       k.offset, v.p, v.stride, v.offset, bias, scale, out, outStride, heads, headDim)
+    do {                                                                                                                \
+        if (rt.p)                                                                                                       \
+            hipLaunchKernelGGL((graphAttention<D16, true>), grid, dim3(kThreads), 0, stream, q.p, q.stride, q.offset,  \
+                               k.p, k.stride, k.offset, v.p, v.stride, v.offset, bias, scale, out, outStride, heads,   \
+                               headDim, rt.p, rt.boardStride, rt.headStride, rt.scale);                                \
+        else                                                                                                            \
+            hipLaunchKernelGGL((graphAttention<D16, false>), grid, dim3(kThreads), 0, stream, q.p, q.stride, q.offset, \
+                               k.p, k.stride, k.offset, v.p, v.stride, v.offset, bias, scale, out, outStride, heads,   \
+                               headDim, (const float*)nullptr, 0L, 0, 0.f);                                            \
+    } while (0)
     switch ((headDim + 15) / 16) {
     case 1: NSG_ATT(1); break;
     case 2: NSG_ATT(2); break;

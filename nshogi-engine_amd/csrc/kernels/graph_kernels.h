@@ -108,7 +108,18 @@ hipError_t launchGraphRmsNorm(DevView in, const float* gamma, float eps, float* 
 // Attention over the 81 squares, one workgroup per (board, head): out[:, h*d .. h*d+d-1] = softmax(scale * q_h k_h^T +
 // bias[h]) v_h.  q, k, v: token views of heads * headDim channels at offsets that are multiples of 4; headDim a
 // multiple of 4, at most kMaxHeadDim; bias: [heads][81][81] or null.
-hipError_t launchGraphAttention(DevView q, DevView k, DevView v, const float* bias, float scale, float* out,
+// rt (p null: none): a bias computed at run time, the element of (board, head, query, key) at p[board * boardStride +
+// head * headStride + query * 81 + key]; headStride 0 broadcasts one bias over the heads, 6561 is a flat [N,H*6561]
+// tensor, 6576 head rows [N,H,6561].  Per score: acc * scale, then + bias, then + rt.scale * rt; with rt.scale > 0
+// (the planner refuses any other factor; the launch rejects it) an element of -inf gives probability exactly 0.  The
+// loads are clamped to query 80 and key 80 of the (board, head) block: nothing outside it is read.
+struct RtBias {
+    const float* p = nullptr;
+    long boardStride = 0;
+    int headStride = 0;
+    float scale = 1.f;
+};
+hipError_t launchGraphAttention(DevView q, DevView k, DevView v, const float* bias, float scale, RtBias rt, float* out,
                                 int outStride, int heads, int headDim, int boards, hipStream_t stream);
 
 // [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)

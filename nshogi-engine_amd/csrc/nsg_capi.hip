@@ -894,13 +894,16 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
             if (prof && convs == 0) NSG_HIP(hipEventRecord(e[1], s));
             gr::DevView res;
             if (L.res.buf != -2) res = dv(L.res);
-            const int groups = L.dense ? (B + 80) / 81 : B;
+            // a dense layer runs over groups of 81 rows: boards, or the (board, head) rows of a head-row tensor
+            const long denseRows = (long)B * L.rowsPerBoard;
+            const int groups = L.dense ? (int)((denseRows + 80) / 81) : B;
             if (L.depthwise)
                 NSG_HIP(gr::launchGraphDepthwise(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out),
                                                  L.out.stride, L.out.C, L.kh, L.kw, L.dh, L.dw, B, L.act, s));
             else if (L.kh == L.kw && (L.kh == 1 || L.kh == 3) && L.dh == 1 && L.dw == 1)
                 NSG_HIP(gr::launchGraphConv(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out), L.out.stride,
-                                            L.out.C, L.cinPad, L.coutTiles, L.taps, groups, rowsOf(L.out), L.act, s));
+                                            L.out.C, L.cinPad, L.coutTiles, L.taps, groups, L.dense ? denseRows : rowsOf(L.out),
+                                            L.act, s));
             else
                 NSG_HIP(gr::launchGraphConvGeo(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out),
                                                L.out.stride, L.out.C, L.cinPad, L.coutTiles, L.kh, L.kw, L.dh, L.dw, B, L.act, s));
@@ -959,10 +962,18 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
         case gr::kLaunchRmsNorm:
             NSG_HIP(gr::launchGraphRmsNorm(dv(L.in), wts + L.wOff, L.eps, ptr(L.out), L.out.stride, rowsOf(L.out), s));
             break;
-        case gr::kLaunchAttention:
+        case gr::kLaunchAttention: {
+            gr::RtBias rt;
+            if (L.hasRtBias) {
+                rt.p = ptr(L.rtBias) + L.rtBias.offset;
+                rt.boardStride = L.rtBias.stride;
+                rt.headStride = L.rtHeadStride;
+                rt.scale = L.rtScale;
+            }
             NSG_HIP(gr::launchGraphAttention(dv(L.in), dv(L.attK), dv(L.attV), L.hasBias ? wts + L.biasOff : nullptr, L.scale,
-                                             ptr(L.out), L.out.stride, L.heads, L.headDim, B, s));
+                                             rt, ptr(L.out), L.out.stride, L.heads, L.headDim, B, s));
             break;
+        }
         case gr::kLaunchFlatten:
             NSG_HIP(gr::launchGraphFlatten(dv(L.in), ptr(L.out), L.out.stride, B, s));
             break;

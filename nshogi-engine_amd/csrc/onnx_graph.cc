@@ -17,7 +17,7 @@ void Planner::run() {
     for (size_t K = 0; K < Nodes.size(); ++K)
         if (!Skip[K]) lower(Nodes[K], K);
     checkOutputs();
-    assignBuffers(P, VirtStride, VirtSpatial);
+    assignBuffers(P, VirtStride, VirtSpatial, VirtAlsoFlat);
 }
 
 // tensor contract (trt.cc:144-227), and the op set
@@ -127,6 +127,12 @@ void Planner::lower(const Node& N, size_t K) {
             fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " exists only inside the GroupNorm pattern: Reshape, InstanceNormalization, Reshape back to [N,C,9,9] (DESIGN.md section 13.3)");
         if (I.runtime && I.form == kFormChanLast)
             fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " is a channel-last view: only a LayerNorm over its last axis and Transpose [0,3,1,2] read it (DESIGN.md section 13.3)");
+        if (I.runtime && I.form == kFormHeadRows) {
+            if (Op == "MatMul" && J == 0 && has(N, 1) && !get(N, 1).runtime) return headRowsDense(N, K);
+            fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " holds head rows [N,H,K]: only a MatMul with a constant [K,M] or the Reshape to an attention bias [N,H,81,81] reads them (DESIGN.md section 13.3)");
+        }
+        if (I.runtime && I.form == kFormScoreBias)
+            fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " is a run-time attention bias: only the Add into the scores of the attention pattern reads it (DESIGN.md section 13.3)");
         if (I.runtime && I.form >= kFormChan3)
             fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " is consumed outside the token-view and attention patterns (DESIGN.md section 13.3)");
     }
@@ -198,7 +204,8 @@ void Planner::checkOutputs() {
 }
 
 // lifetimes -> physical buffers (a launch's output never shares a buffer with its inputs)
-void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::vector<bool>& VirtSpatial) {
+void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::vector<bool>& VirtSpatial,
+                   const std::vector<int>& VirtAlsoFlat) {
     const size_t NV = VirtStride.size();
     const int NL = (int)P.launches.size();
     std::vector<int> Last(NV, -1); // the last launch that touches each virtual buffer (NL: a graph output)
@@ -227,6 +234,8 @@ void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::
         Free[(size_t)Best] = false;
         int& S = VirtSpatial[(size_t)V] ? P.bufSpatialStride[(size_t)Best] : P.bufFlatStride[(size_t)Best];
         S = std::max(S, VirtStride[(size_t)V]);
+        // token rows read as flat rows too: a dense launch reads whole groups of 81 boards at that stride
+        P.bufFlatStride[(size_t)Best] = std::max(P.bufFlatStride[(size_t)Best], VirtAlsoFlat[(size_t)V]);
         Phys[(size_t)V] = Best;
     };
     for (int I = 0; I < NL; ++I) {

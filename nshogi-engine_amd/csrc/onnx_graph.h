@@ -7,6 +7,7 @@
 //   token [N,81,C]              -> the same rows under another logical shape: a transformer's token tensor over the
 //                                  81 squares is the spatial layout, so flatten(2).transpose(1,2) costs no launch
 //   flat [N,C] / [N,C,1,1] / [N] -> [row = board][stride] floats
+//   head rows [N,H,K]           -> [row = board * H + head][stride] floats, a view of a flat [N,H*K] (K a multiple of 16)
 // stride = C rounded up to 16 (the conv kernel's K chunk); channels C..stride-1 are written as zero by every kernel.
 // A view names a buffer plus a channel offset, so `Slice` and `Split` along the channel axis cost no launch.
 #ifndef NSG_ONNX_GRAPH_H
@@ -120,6 +121,17 @@ struct Launch {
     int heads = 0, headDim = 0;
     float scale = 1.f;
     bool hasBias = false;
+    // ... plus rtScale times a bias computed at run time (hasRtBias): rtBias is a flat view whose stride is the floats
+    // from one board to the next; head h, query q, key j at offset + h * rtHeadStride + q * 81 + j of the board's row.
+    // rtHeadStride 0: one bias for all heads ([N,1,81,81]); 6561: a flat [N,H*6561]; 6576: head rows [N,H,6561].
+    // Per score: acc * scale, then + bias, then + rtScale * rtBias, whatever order the graph wrote them in.
+    View rtBias;
+    int rtHeadStride = 0;
+    float rtScale = 1.f;
+    bool hasRtBias = false;
+    // kLaunchConv, dense: the rows of a board.  1: flat [N,K]; H: head rows [N,H,K], rows of (board, head) at stride
+    // in.stride, H of them contiguous per board (the virtual buffer is flat with stride H * in.stride).
+    int rowsPerBoard = 1;
 };
 
 struct GraphPlan {

@@ -70,6 +70,12 @@ void dump(const GraphPlan& P) {
         view("attK", L.attK);
         view("attV", L.attV);
         std::printf(" heads=%d headDim=%d scale=%a hasBias=%d", L.heads, L.headDim, (double)L.scale, L.hasBias);
+        // the fields of a run-time attention bias and of a dense launch over head rows, where they are not the defaults
+        if (L.hasRtBias) {
+            view("rtBias", L.rtBias);
+            std::printf(" rtHeadStride=%d rtScale=%a", L.rtHeadStride, (double)L.rtScale);
+        }
+        if (L.rowsPerBoard != 1) std::printf(" rowsPerBoard=%d", L.rowsPerBoard);
         std::printf(" srcs=%zu", L.srcs.size());
         for (const EltSrc& S : L.srcs) {
             std::printf(" [mode=%d", S.mode);

@@ -46,6 +46,8 @@ enum Form {
     kFormTokOut4, // [N,81,H,d]
     kFormGroup3,  // [N,G,M], G M = C 81: the groups of a GroupNorm, between its two Reshapes only ([N,C,81] when G = C)
     kFormChanLast, // [N,9,9,C]: the spatial rows once more, for a LayerNorm over the channels between two Transposes
+    kFormHeadRows, // [N,H,K]: rows of (board, head), a view of a flat [N,H*K]; read by a MatMul with a constant [K,M] only
+    kFormScoreBias, // [N,H,81,81] or [N,1,81,81]: a flat or head-row tensor as the run-time bias of attention scores
 };
 inline bool isAttForm(int F) { return F >= kFormTok4 && F <= kFormTokOut4; }
 
@@ -65,6 +67,13 @@ struct Val {
     double scale = 1.0;         // scalar factors folded so far
     View attQ, attK, attV;      // kFormScores and later: the q and k token views; kFormHeadOut and later: v's
     std::vector<double> bias;   // kFormScores and later: [H][81][81], empty = none
+    // kFormScores and later: the run-time bias (hasRt), added as rtScale * rtBias.  kFormScoreBias: v is the view (its
+    // stride the floats from board to board) and rtHead the floats from head to head, 0 for [N,1,81,81]
+    bool hasRt = false;
+    View rtBias;
+    int rtHead = 0;
+    double rtScale = 1.0;
+    int headRows = 0;           // kFormHeadRows: H; v.stride is the stride of one (board, head) row, v.C = K
     std::string chain;          // names of the nodes absorbed so far
     // the GroupNorm pattern's state ([N,G,M] behind its InstanceNormalization, until the Reshape back)
     int normG = 0;              // > 0: normalised per group, not yet launched
@@ -109,6 +118,7 @@ template <class Fn> void forEachView(Launch& L, Fn F) {
     F(L.res);
     F(L.attK);
     F(L.attV);
+    F(L.rtBias);
     for (EltSrc& S : L.srcs)
         if (S.mode == kSrcSame || S.mode == kSrcBoard) F(S.v);
     for (CopySeg& S : L.segs) F(S.v);
@@ -117,7 +127,9 @@ template <class Fn> void forEachView(Launch& L, Fn F) {
 
 // Lifetimes -> physical buffers: renames the virtual buffers of the launches' views and of the three output views,
 // and fills the plan's buffer stride tables (onnx_graph.cc).
-void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::vector<bool>& VirtSpatial);
+// VirtAlsoFlat: the flat stride a spatial virtual buffer is also read at (a token tensor viewed as flat rows), 0 = none.
+void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::vector<bool>& VirtSpatial,
+                   const std::vector<int>& VirtAlsoFlat);
 
 // A linear layer's weights as read from the model, W[cout][CinW][taps], before packing (planner_linear.cc)
 struct LinearW {
@@ -148,6 +160,7 @@ class Planner {
     std::vector<Group> Groups;
     std::vector<int> VirtStride;     // per produced tensor (virtual buffer)
     std::vector<bool> VirtSpatial;
+    std::vector<int> VirtAlsoFlat;   // see assignBuffers
 
     [[noreturn]] void fail(const Node& N, const std::string& Why) const {
         throw Error("node '" + N.Name + "' (" + N.Op + "): " + Why);
@@ -173,6 +186,7 @@ class Planner {
     int newVirt(int Stride, bool Spatial) {
         VirtStride.push_back(Stride);
         VirtSpatial.push_back(Spatial);
+        VirtAlsoFlat.push_back(0);
         return (int)VirtStride.size() - 1;
     }
     View freshView(int C, bool Spatial) {
@@ -315,6 +329,8 @@ class Planner {
     bool formView(const Node& N);   // Transpose, and Reshape / Flatten to or from the forms above
     Val headsSource(const Node& N, const Val& X0);
     void attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND);
+    bool flatFormView(const Node& N, const Val& X0); // token -> flat, flat -> head rows, flat / head rows -> score bias
+    void headRowsDense(const Node& N, size_t Index); // MatMul of head rows [N,H,K] with a constant [K,M]
     bool attentionOp(const Node& N); // MatMul / Mul / Div / Add / Softmax on the attention pattern's 4-D tensors
     void viewOp(const Node& N);     // Flatten / Reshape / Squeeze / Unsqueeze / Identity on a spatial or flat tensor
     void concat(const Node& N);

@@ -218,4 +218,46 @@ void Planner::linear(const Node& N, size_t Index) {
     Vals[E.out] = V;
 }
 
+// ---- MatMul of head rows [N,H,K] with a constant [K,M]: the dense form of graphConv<1> over N * H rows -----------------
+// The rows of (board, head) lie H to a board at stride K, so the launch is a dense layer whose row count is boards * H;
+// the result is head rows [N,H,M] in a flat virtual buffer of stride H * (M rounded up to 16).  The epilogue takes the
+// constant per-channel Adds and one activation; a residual is not absorbed (the Add is then refused as a reader of head rows).
+void Planner::headRowsDense(const Node& N, size_t Index) {
+    const Val X = get(N, 0);
+    const int H = X.headRows;
+    LinearW Lw = denseWeights(N, X, true);
+    const int Cout = Lw.Cout;
+    const std::vector<int64_t> Dims{kBatch, H, Cout};
+    const Epilogue E = foldEpilogue(N, Index, Dims, 2, -1, &Lw);
+    Launch L;
+    L.kind = kLaunchConv;
+    L.name = E.name;
+    L.dense = true;
+    L.rowsPerBoard = H;
+    L.taps = L.kh = L.kw = 1;
+    L.in = X.v;
+    L.cinPad = roundUp(Lw.Cin, kChunk);
+    L.coutTiles = (Cout + kCoutTile - 1) / kCoutTile;
+    L.act = E.act;
+    L.res.buf = kNoRes;
+    std::vector<float> Pk, Bf;
+    packDense(Lw, L.cinPad / kChunk, L.coutTiles, &Pk, &Bf);
+    L.wOff = addConst(Pk);
+    L.biasOff = addConst(Bf);
+    L.out.stride = roundUp(Cout, kChunk);
+    L.out.C = Cout;
+    L.out.spatial = false;
+    L.out.buf = newVirt(H * L.out.stride, false);
+    P.flopsPerPosition += 2.0 * H * (double)Lw.Cin * Cout;
+    Val V;
+    V.runtime = true;
+    V.dims = Dims;
+    V.form = kFormHeadRows;
+    V.headRows = H;
+    V.v = L.out;
+    V.producer = N.Name;
+    emit(L);
+    Vals[E.out] = V;
+}
+
 } // namespace nsg::graph

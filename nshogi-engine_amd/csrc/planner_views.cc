@@ -95,7 +95,7 @@ bool Planner::formView(const Node& N) {
     // Reshape / Flatten
     const int F = X0.form;
     const bool PlainSpatial = F == kFormPlain && !X0.flatOfSpatial && isSpatialDims(X0.dims);
-    if (F == kFormPlain && !PlainSpatial) return false;
+    if (F == kFormPlain && !PlainSpatial) return flatFormView(N, X0);
     if (PlainSpatial) {
         // only Reshape to [N,C,81] is taken here (torch's flatten(2)); every other view is the existing code's.  ONNX's
         // own Flatten with axis 2 gives [N*C,81], which mixes boards, and is refused there.
@@ -120,6 +120,7 @@ bool Planner::formView(const Node& N) {
         V.chain.clear();
         return set(V, kFormChan3, ND);
     }
+    if ((F == kFormToken || F == kFormHeadRows) && flatFormView(N, X0)) return true;
     if (Op == "Flatten" && !(F == kFormChan3 && N.attrI("axis", 1) == 1))
         fail(N, "Flatten of " + dimsStr(X0.dims) + " is outside the token-view patterns");
     if (X0.normG > 0) { // the Reshape that closes the GroupNorm pattern: one launch, with what follows it
@@ -164,6 +165,83 @@ bool Planner::formView(const Node& N) {
         return true;
     }
     fail(N, "Reshape of " + dimsStr(X0.dims) + " is outside the token-view and attention patterns (DESIGN.md section 13.3)");
+}
+
+// The views around a bias generator, none of which costs a launch:
+//   token [N,81,C] -> flat [N,81*C] in the tokens' own order sq * C + c, C a multiple of 16: a board's 81 rows are contiguous
+//   flat [N,H*K] -> head rows [N,H,K], K a multiple of 16: rows of (board, head) at stride K
+//   flat [N,H*6561] or [N,6561], head rows [N,H,6561] -> the run-time attention bias [N,H,81,81] or [N,1,81,81]
+// Returns false when N is none of them (the caller goes on, and refuses what nothing takes).
+bool Planner::flatFormView(const Node& N, const Val& X0) {
+    const int F = X0.form;
+    auto put = [&](Val V, int Form, const std::vector<int64_t>& Dims) {
+        V.form = Form;
+        V.dims = Dims;
+        V.producer = N.Name;
+        V.chain.clear();
+        V.group = -1;
+        Vals[N.Out[0]] = V;
+        return true;
+    };
+    if (F == kFormToken) {
+        const int64_t C = X0.dims[2];
+        if (N.Op == "Flatten" ? N.attrI("axis", 1) != 1 : reshapeTarget(N, X0.dims) != std::vector<int64_t>{kBatch, 81 * C}) return false;
+        if (C % kChunk != 0)
+            fail(N, "a token tensor " + dimsStr(X0.dims) + " flattened to [N," + std::to_string(81 * C) + "]: a board's 81 rows are contiguous only when C is a multiple of " +
+                        std::to_string(kChunk) + " (C = " + std::to_string(C) + ")");
+        const View Src = plain(N.In[0], N.Name + " (input copy)");
+        if (Src.buf < 0) fail(N, "the graph input viewed as tokens cannot be flattened in the tokens' order");
+        VirtAlsoFlat[(size_t)Src.buf] = std::max(VirtAlsoFlat[(size_t)Src.buf], (int)(81 * C));
+        Val V = Vals.at(N.In[0]);
+        V.v.stride = V.v.C = (int)(81 * C);
+        V.v.spatial = false;
+        return put(V, kFormPlain, {kBatch, 81 * C});
+    }
+    if (N.Op != "Reshape") {
+        if (F == kFormHeadRows) fail(N, N.Op + " of head rows " + dimsStr(X0.dims) + ": only a MatMul with a constant [K,M] or the Reshape to an attention bias [N,H,81,81] reads them");
+        return false;
+    }
+    if (F == kFormHeadRows) {
+        const std::vector<int64_t> ND = reshapeTarget(N, X0.dims);
+        const int64_t H = X0.headRows;
+        if (ND != std::vector<int64_t>{kBatch, H, 81, 81})
+            fail(N, "head rows " + dimsStr(X0.dims) + " can become an attention bias [N,H,81,81] (K = 6561), not " + dimsStr(ND));
+        Val V = X0;
+        V.rtHead = H == 1 ? 0 : X0.v.stride;
+        V.v.stride = (int)H * X0.v.stride;
+        V.v.C = (int)H * X0.v.stride;
+        V.headRows = 0;
+        return put(V, kFormScoreBias, ND);
+    }
+    if (X0.flatOfSpatial || X0.dims.size() != 2 || flatC(X0.dims) <= 0) return false;
+    const Val& ShV = get(N, 1);
+    if (ShV.runtime) return false;
+    const std::vector<int64_t> ND = reshapeTarget(N, X0.dims);
+    if (flatC(ND) >= 0) return false;
+    if (ND.size() == 3) {
+        const int64_t H = ND[1], K = ND[2];
+        if (H <= 0 || K <= 0) return false;
+        // head rows only where something reads them as such -- a MatMul (its data input) or the score-bias Reshape;
+        // any other [N,A,B] of a flat tensor keeps the refusal it had
+        bool Read = false;
+        for (size_t J = indexOf(&N) + 1; J < Nodes.size(); ++J)
+            Read = Read || (!Skip[J] && (Nodes[J].Op == "MatMul" || Nodes[J].Op == "Reshape") && !Nodes[J].In.empty() && Nodes[J].In[0] == N.Out[0]);
+        if (!Read) return false;
+        if (K % kChunk != 0)
+            fail(N, "head rows " + dimsStr(ND) + " of a flat " + dimsStr(X0.dims) + ": the rows of (board, head) are rows of the layout only when K is a multiple of " +
+                        std::to_string(kChunk) + " (K = " + std::to_string(K) + ")");
+        plain(N.In[0], N.Name + " (input copy)");
+        Val V = Vals.at(N.In[0]);
+        V.v.stride = V.v.C = (int)K;
+        V.headRows = (int)H;
+        return put(V, kFormHeadRows, ND);
+    }
+    if (ND.size() == 4 && ND[1] > 0 && ND[2] == 81 && ND[3] == 81) {
+        Val V = ready(N.In[0]);
+        V.rtHead = ND[1] == 1 ? 0 : 81 * 81;
+        return put(V, kFormScoreBias, ND);
+    }
+    return false;
 }
 
 // The token tensor a Reshape splits into heads.  q * scale (or k * scale) right before the split: an open group of one
@@ -212,6 +290,12 @@ void Planner::attentionLaunch(const Node& N, const Val& X0, const std::vector<in
     if (L.hasBias) {
         std::vector<float> Bf(X0.bias.begin(), X0.bias.end());
         L.biasOff = addConst(Bf);
+    }
+    L.hasRtBias = X0.hasRt;
+    if (L.hasRtBias) {
+        L.rtBias = X0.rtBias;
+        L.rtHeadStride = X0.rtHead;
+        L.rtScale = (float)X0.rtScale;
     }
     L.out = freshView((int)(H * Hd), true);
     P.flopsPerPosition += 2.0 * (2.0 * 81 * 81 * (double)Hd) * (double)H; // q k^T and probs x v
@@ -279,7 +363,27 @@ bool Planner::attentionOp(const Node& N) {
     const bool AR = isAttForm(FA);
     const Val& T = AR ? A : *B;
     const Val& Cst = AR ? *B : A;
-    if (Cst.runtime) fail(N, "the other operand of " + Op + " on " + dimsStr(T.dims) + " is computed at run time: only constants enter the attention pattern");
+    if (Cst.runtime) {
+        // one bias computed at run time, a view of a flat or head-row tensor, added to the scores
+        if (Op != "Add" || T.form != kFormScores)
+            fail(N, "the other operand of " + Op + " on " + dimsStr(T.dims) + " is computed at run time: only constants enter the attention pattern, and one run-time bias its scores");
+        if (Cst.form != kFormScoreBias)
+            fail(N, "a run-time tensor " + dimsStr(Cst.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)Cst.v.C * 81} : Cst.dims) + " ('" + N.In[AR ? 1 : 0] +
+                        "') is added to the attention scores " + dimsStr(T.dims) + ": only a Reshape of a flat or head-row tensor to [N,H,81,81] or [N,1,81,81] is a run-time bias (DESIGN.md section 13.3)");
+        if (T.hasRt) fail(N, "a second run-time Add on the attention scores: the pattern takes one run-time bias");
+        const int64_t H = T.dims[1], BH = Cst.dims[1];
+        if (BH != H && BH != 1)
+            fail(N, "the run-time bias " + dimsStr(Cst.dims) + " has " + std::to_string(BH) + " heads, the attention scores " + dimsStr(T.dims) + " have " + std::to_string(H));
+        interior(N, 0);
+        interior(N, 1);
+        if (Cst.v.offset + (BH - 1) * (int64_t)Cst.rtHead + 81 * 81 > Cst.v.stride) fail(N, "internal planner error: the run-time bias does not fit its rows");
+        Val V = T;
+        V.hasRt = true;
+        V.rtBias = Cst.v;
+        V.rtHead = Cst.rtHead;
+        V.rtScale = 1.0;
+        return put(V, kFormScores, T.dims);
+    }
     interior(N, AR ? 0 : 1);
     if (Op == "Mul" || Op == "Div") {
         if (Cst.count() != 1) fail(N, "only a scalar constant scales the attention pattern's tensors");
@@ -287,9 +391,12 @@ bool Planner::attentionOp(const Node& N) {
         if (T.form != kFormTok4 && T.form != kFormHeads && T.form != kFormHeadsT && T.form != kFormScores)
             fail(N, Op + " on " + dimsStr(T.dims) + " is outside the attention pattern");
         const double S = Op == "Mul" ? Cst.at(0) : 1.0 / Cst.at(0);
+        // (a factor <= 0 would turn a run-time -inf, a closed key, into +inf or NaN)
+        if (T.hasRt && !(S > 0.0)) fail(N, "a scalar factor of " + std::to_string(S) + " behind the run-time Add on the attention scores: only a positive factor scales a run-time bias");
         Val V = T;
         V.scale *= S;
         for (double& Bv : V.bias) Bv *= S;
+        if (V.hasRt) V.rtScale *= S; // a factor in front of the run-time Add leaves that bias alone
         return put(V, T.form, T.dims);
     }
     // Add: a constant bias on the scores

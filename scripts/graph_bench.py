@@ -13,6 +13,9 @@
     python scripts/graph_bench.py --trace-norm      # GroupNorm at three group counts, a max pool and a depthwise 3x3
     python scripts/graph_bench.py --summarize-norm DIR/run_results.db [--out profiles/graph/norm_bench.json]
     python scripts/graph_bench.py --mish [--out profiles/graph/mish_bench.json] [--repeats 3]   # the Mish row
+    python scripts/graph_bench.py --smolgen [--out profiles/graph/smolgen_bench.json] [--repeats 3]   # the run-time bias row
+    python scripts/graph_bench.py --trace-smolgen      # both transformers at B = 512 for `rocprofv3 --kernel-trace`
+    python scripts/graph_bench.py --summarize-smolgen DIR/run_results.db   # graphAttention with and without the bias
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
@@ -38,6 +41,12 @@ timed `--repeats` times in turn; the file holds every repeat, so the run's sprea
 
 --attention: a pre-LN transformer over the 81 squares (tests/golden/make_onnx_attention_golden.py's PreNet with 8
 blocks, F = 256, H = 8 heads of d = 32, FFN width 1024), exported at run time, on the general path.
+
+--smolgen: the --attention transformer with a bias generator in every block (tests/attention_bias_models.py's
+SmolgenPreNet: token Linear(256,32), flatten, Linear(2592,256) + swish, Linear(256,8x64), LayerNorm, head rows, one shared
+Linear(64,6561), the Add into the scores), beside the plain --attention net, each timed `--repeats` times in turn.
+--trace-smolgen runs both at B = 512 in one process; --summarize-smolgen prints the median and range of every
+graphAttention instantiation (`<2, false>`: no run-time bias, `<2, true>`: with one) and of the head-row dense launch.
 """
 import argparse
 import importlib
@@ -50,6 +59,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def family_onnx(nsg, path):
@@ -124,6 +134,28 @@ def attention_onnx(path):
     torch.manual_seed(6)
     net = mk.randomize(mk.PreNet(C=86, F=256, H=8, ffn=1024, VH=256, blocks=8), 14).eval()
     mk.export_model(net, path)
+
+
+def smolgen_onnx(path):
+    import torch
+    import attention_bias_models as abm
+    import make_onnx_attention_golden as mk
+    torch.manual_seed(16)
+    mk.export_model(mk.randomize(abm.SmolgenPreNet(), 24).eval(), path)
+
+
+def summarize_smolgen(db):
+    """graphAttention per instantiation (a --trace-attention or --trace-smolgen run): launches, median, range in us."""
+    import sqlite3
+    import statistics
+    c = sqlite3.connect(db)
+    by = {}
+    for n, t in c.execute("select name, end-start from kernels"):
+        if "graphAttention" in n or "graphConv<1>" in n:
+            short = n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+            by.setdefault(short, []).append(t / 1e3)
+    for n, ts in sorted(by.items()):
+        print(f"{n:50s} n={len(ts):5d} median {statistics.median(ts):9.1f} us  min {min(ts):9.1f}  max {max(ts):9.1f}")
 
 
 def rate(nsg, path, batch, prec="fp32", force=False, iters=50, warmup=5):
@@ -306,8 +338,14 @@ def main():
     ap.add_argument("--trace-norm", action="store_true", help="GroupNorm of 32, 256 and 1 groups, a 3x3 max pool and a depthwise 3x3 at B=512, C=256")
     ap.add_argument("--summarize-norm", metavar="DB", help="summarise the rocprofv3 database of a --trace-norm run")
     ap.add_argument("--mish", action="store_true", help="the 20x256 net with Mish, the same net with swish, and the forced family net")
-    ap.add_argument("--repeats", type=int, default=3, help="--mish: times each (net, batch) is timed")
+    ap.add_argument("--repeats", type=int, default=3, help="--mish, --smolgen: times each (net, batch) is timed")
+    ap.add_argument("--smolgen", action="store_true", help="the transformer with a run-time attention bias per block, and without")
+    ap.add_argument("--trace-smolgen", action="store_true", help="both at B=512, 13 forwards each")
+    ap.add_argument("--summarize-smolgen", metavar="DB", help="graphAttention medians of a --trace-smolgen / --trace-attention run")
     a = ap.parse_args()
+    if a.summarize_smolgen:
+        summarize_smolgen(a.summarize_smolgen)
+        return
     if a.summarize_norm:
         summarize_norm(a.summarize_norm, a.out.replace("graph_bench.json", "norm_bench.json"))
         return
@@ -330,6 +368,30 @@ def main():
             make(path)
             r, info = rate(nsg, path, TRACE_BATCH, iters=POOL_FAMILY_FORWARDS - 3, warmup=3)
             print(json.dumps({label: r, "launches": info["launches"]}), flush=True)
+        return
+    if a.smolgen or a.trace_smolgen:
+        paths = {"smolgen_8x256_general": os.path.join(tmp, "smolgen.onnx"), "attention_8x256_general": os.path.join(tmp, "att.onnx")}
+        smolgen_onnx(paths["smolgen_8x256_general"])
+        attention_onnx(paths["attention_8x256_general"])
+        if a.trace_smolgen:
+            for k, path in paths.items():
+                r, info = rate(nsg, path, TRACE_BATCH, iters=10, warmup=3)
+                print(json.dumps({k: r, "launches": info["launches"]}), flush=True)
+            return
+        rows = {k: {} for k in paths}
+        for b in [int(b) for b in a.batches.split(",")]:
+            for rep in range(a.repeats):
+                for k, path in paths.items():
+                    r, info = rate(nsg, path, b, iters=20 if b >= 256 else 50)
+                    rows[k].setdefault(str(b), []).append(round(r, 1))
+                    rows[k].update(path=info["path"], launches=info["launches"], attention_launches=info["attention_launches"],
+                                   flops_per_position=info["flops_per_position"])
+        for k, row in rows.items():
+            print(k, json.dumps(row), flush=True)
+        out = a.out.replace("graph_bench.json", "smolgen_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump({"repeats": a.repeats, "rows": rows}, f, indent=1)
         return
     if a.mish:
         paths = {k: os.path.join(tmp, k + ".onnx") for k in ("mish_20x256_general", "swish_20x256_general", "family_20x256_general")}
