@@ -125,7 +125,13 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    optional [N,H,K] stage with one Linear shared by the heads (K a multiple of
  *    16), and a Reshape into the scores' shape; the attention still is one
  *    launch.  A mask input and nn.MultiheadAttention's own export form stay
- *    refused.  A general graph always runs in
+ *    refused.  Outside that pattern a MatMul of two run-time token tensors is
+ *    one launch of its own: [N,81,K] x [N,K,81] (an attention policy head's
+ *    from . to^T, a Gram matrix x x^T) and [N,81,81] x [N,81,M], any K and M,
+ *    with constant scalar Mul / Div nodes and one activation behind it folded
+ *    in (sigmoid or ReLU attention without a head split is two launches); a
+ *    transposed first operand, flat or spatial operands and a Softmax on the
+ *    result stay refused.  A general graph always runs in
  *    exact fp32, whatever nsg_set_precision asked for.
  * When both refuse, the load fails with NSG_E_FORMAT and a message giving both
  * reasons, the general path's naming the node (the reference's parser

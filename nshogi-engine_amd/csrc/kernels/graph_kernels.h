@@ -1,5 +1,5 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
-// graph_ops.hip, graph_attention.hip, graph_norm.hip).
+// graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -121,6 +121,16 @@ struct RtBias {
 };
 hipError_t launchGraphAttention(DevView q, DevView k, DevView v, const float* bias, float scale, RtBias rt, float* out,
                                 int outStride, int heads, int headDim, int boards, hipStream_t stream);
+
+// The product of two run-time token tensors per board (graph_bmm.hip), out = act(scale * sum): the sum is one f32 chain
+// over k ascending that depends on (K, M) only, then one multiplication by `scale`, then a parameter-free Act.  Views
+// at offsets that are multiples of 4, of any width >= 1; pad channels of `out` are written as zeros.
+// NT: a, b [boards*81][K] -> out[n,i,j] = sum_k a[n,i,k] b[n,j,k], 81 channels at outStride = 96.
+hipError_t launchGraphBmmNT(DevView a, DevView b, float scale, int act, float* out, int outStride, int boards,
+                            hipStream_t stream);
+// NN: p [boards*81][81], v [boards*81][M] -> out[n,i,c] = sum_j p[n,i,j] v[n,j,c], outStride = M rounded up to 16.
+hipError_t launchGraphBmmNN(DevView p, DevView v, float scale, int act, float* out, int outStride, int boards,
+                            hipStream_t stream);
 
 // [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)
 hipError_t launchGraphFlatten(DevView in, float* out, int outStride, int boards, hipStream_t stream);

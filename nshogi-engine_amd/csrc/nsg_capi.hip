@@ -977,6 +977,10 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
         case gr::kLaunchFlatten:
             NSG_HIP(gr::launchGraphFlatten(dv(L.in), ptr(L.out), L.out.stride, B, s));
             break;
+        case gr::kLaunchBmm:
+            if (L.bmmNN) NSG_HIP(gr::launchGraphBmmNN(dv(L.in), dv(L.bmmB), L.scale, L.act, ptr(L.out), L.out.stride, B, s));
+            else NSG_HIP(gr::launchGraphBmmNT(dv(L.in), dv(L.bmmB), L.scale, L.act, ptr(L.out), L.out.stride, B, s));
+            break;
         default:
             return fail(NSG_E_INVALID, "internal error: unknown launch kind %d in the graph plan", L.kind);
         }

@@ -119,6 +119,7 @@ void Planner::lower(const Node& N, size_t K) {
     const Val& X = get(N, 0);
     double PowOne = 0;
     if (formView(N) || attentionOp(N) || normOp(N, K)) return;
+    if (bmmOperands(N)) return bmm(N, K);
     // [N,C,81] and the 4-D tensors exist only inside the patterns the calls above follow
     for (size_t J = 0; J < N.In.size(); ++J) {
         if (N.In[J].empty()) continue;

@@ -74,7 +74,7 @@ struct EltSrc {
 
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
-    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm
+    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm
 };
 // kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
@@ -132,6 +132,14 @@ struct Launch {
     // kLaunchConv, dense: the rows of a board.  1: flat [N,K]; H: head rows [N,H,K], rows of (board, head) at stride
     // in.stride, H of them contiguous per board (the virtual buffer is flat with stride H * in.stride).
     int rowsPerBoard = 1;
+    // kLaunchBmm: the product of two run-time token tensors per board, out = act(scale * sum), the sum first, then the
+    // scalar, then `act` (a parameter-free Act).  A = `in`, B = `bmmB`, both token views at offsets that are multiples of 4.
+    // NT (bmmNN false): A [N,81,bmmK], B [N,81,bmmK] (the rows of the graph's [N,K,81] operand), out[n,i,j] = sum_k
+    // A[n,i,k] B[n,j,k], a token tensor of 81 channels.  NN: A [N,81,81], B [N,81,M], out[n,i,c] = sum_j A[n,i,j] B[n,j,c],
+    // bmmK = 81.
+    View bmmB;
+    bool bmmNN = false;
+    int bmmK = 0;
 };
 
 struct GraphPlan {

@@ -76,6 +76,10 @@ void dump(const GraphPlan& P) {
             std::printf(" rtHeadStride=%d rtScale=%a", L.rtHeadStride, (double)L.rtScale);
         }
         if (L.rowsPerBoard != 1) std::printf(" rowsPerBoard=%d", L.rowsPerBoard);
+        if (L.kind == kLaunchBmm) { // A is `in`; scale and act are printed above
+            view("bmmB", L.bmmB);
+            std::printf(" bmmNN=%d bmmK=%d", L.bmmNN, L.bmmK);
+        }
         std::printf(" srcs=%zu", L.srcs.size());
         for (const EltSrc& S : L.srcs) {
             std::printf(" [mode=%d", S.mode);

@@ -119,6 +119,7 @@ template <class Fn> void forEachView(Launch& L, Fn F) {
     F(L.attK);
     F(L.attV);
     F(L.rtBias);
+    F(L.bmmB);
     for (EltSrc& S : L.srcs)
         if (S.mode == kSrcSame || S.mode == kSrcBoard) F(S.v);
     for (CopySeg& S : L.segs) F(S.v);
@@ -331,6 +332,8 @@ class Planner {
     void attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND);
     bool flatFormView(const Node& N, const Val& X0); // token -> flat, flat -> head rows, flat / head rows -> score bias
     void headRowsDense(const Node& N, size_t Index); // MatMul of head rows [N,H,K] with a constant [K,M]
+    bool bmmOperands(const Node& N) const;           // a MatMul of two run-time tensors outside the other patterns
+    void bmm(const Node& N, size_t Index);           // ... as one kLaunchBmm (planner_linear.cc)
     bool attentionOp(const Node& N); // MatMul / Mul / Div / Add / Softmax on the attention pattern's 4-D tensors
     void viewOp(const Node& N);     // Flatten / Reshape / Squeeze / Unsqueeze / Identity on a spatial or flat tensor
     void concat(const Node& N);

@@ -260,4 +260,93 @@ void Planner::headRowsDense(const Node& N, size_t Index) {
     Vals[E.out] = V;
 }
 
+// ---- MatMul of two run-time token tensors: one kLaunchBmm ("run-time products") ---------------
+// Taken when both inputs are run-time tensors that are spatial, flat, token or [N,C,81] tensors; the attention
+// pattern's 4-D tensors went to attentionOp before, and every other form keeps the refusal it had.
+bool Planner::bmmOperands(const Node& N) const {
+    if (N.Op != "MatMul" || N.In.size() != 2) return false;
+    for (const std::string& I : N.In) {
+        auto It = Vals.find(I);
+        if (It == Vals.end() || !It->second.runtime || It->second.normG > 0) return false;
+        const int F = It->second.form;
+        if (F != kFormPlain && F != kFormToken && F != kFormChan3) return false;
+    }
+    return true;
+}
+
+void Planner::bmm(const Node& N, size_t Index) {
+    const Val A0 = get(N, 0), B0 = get(N, 1);
+    auto shown = [](const Val& V) { return dimsStr(V.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)V.v.C * 81} : V.dims); };
+    const std::string Shapes = "MatMul of " + shown(A0) + " and " + shown(B0) + ", both computed at run time: ";
+    if (A0.form == kFormChan3 && B0.form != kFormPlain)
+        fail(N, Shapes + "the first operand is transposed ([N,K,81] x [N,81,M]); only [N,81,K] x [N,K,81] and [N,81,81] x [N,81,M] are run-time products (DESIGN.md section 13.3)");
+    if (A0.form != kFormToken || B0.form == kFormPlain)
+        fail(N, Shapes + "a flat or spatial operand; a run-time product takes token tensors [N,81,C], the second one also as [N,K,81] (DESIGN.md section 13.3)");
+    const bool NN = B0.form == kFormToken;
+    const int64_t Inner = A0.dims[2], BInner = NN ? 81 : B0.dims[1];
+    if (Inner != BInner)
+        fail(N, Shapes + "the inner dimensions disagree (" + std::to_string(Inner) + " and " + std::to_string(BInner) + ")");
+    if (!NN) { // [N,K,81] is never materialised: this MatMul is its one reader
+        auto U = Uses.find(N.In[1]);
+        auto S = ShapeUses.find(N.In[1]);
+        const int Data = (U == Uses.end() ? 0 : U->second) - (S == ShapeUses.end() ? 0 : S->second);
+        if (Outputs.count(N.In[1]) || Data != 1)
+            fail(N, Shapes + "'" + N.In[1] + "' " + shown(B0) + " has a second consumer; a [N,K,81] tensor is a view for one reader");
+    }
+    // a view at a multiple of 4 is read where it lies, any other is copied into rows of its own first
+    auto operand = [&](const std::string& Name) {
+        const View V0 = ready(Name).v;
+        if (V0.offset % 4 == 0) return V0;
+        Launch L;
+        L.kind = kLaunchConcat;
+        L.name = N.Name + " (input copy)";
+        CopySeg S;
+        S.v = V0;
+        L.segs.push_back(S);
+        L.out = freshView(V0.C, true);
+        const View Out = L.out;
+        emit(L);
+        Vals[Name].v = Out;
+        return Out;
+    };
+    Launch L;
+    L.kind = kLaunchBmm;
+    L.in = operand(N.In[0]);
+    L.bmmB = operand(N.In[1]);
+    L.bmmNN = NN;
+    L.bmmK = (int)Inner;
+    L.res.buf = kNoRes;
+    const int Cout = NN ? (int)B0.dims[2] : 81;
+    // the epilogue: constant scalar Mul / Div nodes, then at most one parameter-free activation
+    std::string Name = N.Name, Cur = N.Out[0];
+    double Scale = 1.0;
+    size_t At = Index;
+    while (absorbable(Cur)) {
+        const Node* C = onlyConsumer(Cur, At);
+        if (!C) break;
+        double S = 0;
+        if ((C->Op == "Mul" || C->Op == "Div") && C->In.size() == 2 && C->In[0] != C->In[1] &&
+            (C->In[0] == Cur || C->Op == "Mul") && scalarAhead(C->In[0] == Cur ? C->In[1] : C->In[0], &S)) {
+            Scale = C->Op == "Mul" ? Scale * S : Scale / S;
+        } else if (!C->In.empty() && C->In[0] == Cur && nodeAct(*C) != kActNone) {
+            L.act = nodeAct(*C);
+        } else {
+            break;
+        }
+        Name += "+" + C->Name;
+        Skip[indexOf(C)] = true;
+        At = indexOf(C);
+        Cur = C->Out[0];
+        if (L.act != kActNone) break;
+    }
+    L.name = Name;
+    L.scale = (float)Scale;
+    L.out = freshView(Cout, true);
+    P.flopsPerPosition += 2.0 * 81 * 81 * (double)(NN ? Cout : Inner);
+    Val V = runtimeVal(N, {kBatch, 81, Cout}, kFormToken);
+    V.v = L.out;
+    emit(L);
+    Vals[Cur] = V;
+}
+
 } // namespace nsg::graph
