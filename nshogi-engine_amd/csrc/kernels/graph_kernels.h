@@ -1,5 +1,5 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
-// graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip).
+// graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -48,6 +48,7 @@ struct EltArgs {
     int stride[kMaxEltSrcs];
     int offset[kMaxEltSrcs];
     int mode[kMaxEltSrcs];  // EltMode; kSrcChannel and kSrcSquareChannel read constants at src
+    int bufLines[kMaxEltSrcs], line0[kMaxEltSrcs]; // kSrcRankLine, kSrcFileLine, kSrcLine: the view's line fields
     float scalar[kMaxEltSrcs];
     uint32_t code[kMaxEltCode]; // op | dst << 8 | a << 16 | b << 24
     int ncode;
@@ -56,6 +57,7 @@ struct EltArgs {
     int outStride;
     int C;
     long rows;
+    int outLines; // kSrcLine: the lines per board of the output (and of every such source)
 };
 hipError_t launchGraphElt(const EltArgs& a, hipStream_t stream);
 
@@ -72,6 +74,14 @@ hipError_t launchGraphMax(DevView in, float* out, int outStride, int boards, hip
 // number of taps on the board (kPoolAvgExclude).
 hipError_t launchGraphPool(DevView in, float* out, int outStride, int kh, int kw, int dh, int dw, int mode, int boards,
                            hipStream_t stream);
+
+// Rank and file pooling: the max (kPoolMax) or the mean (kPoolAvgInclude) of each of a board's nine ranks over its files
+// (files = 0) or of each of its nine files over its ranks (files = 1).  `in`: a spatial view at any channel offset (an
+// offset that is no multiple of 4 is read with scalar loads).  out: line rows, row (board, l) at out + ((size_t)board *
+// bufLines + line0 + l) * outStride with 9 <= line0 + 9 <= bufLines; outStride = C rounded up to 16, pad channels zero.
+// The mean is the f32 sum of the line's nine elements in ascending square order, then one division by 9.
+hipError_t launchGraphLinePool(DevView in, float* out, int outStride, int bufLines, int line0, int files, int mode,
+                               int boards, hipStream_t stream);
 
 // Channel concat (also a plain copy of one view): up to kMaxCopySegs views placed at channel dstOff[i]
 struct ConcatArgs {

@@ -36,6 +36,15 @@ __global__ __launch_bounds__(kThreads) void graphElt(EltArgs a) {
             case kSrcBoard: v = p[(size_t)(row / 81) * a.stride[x] + a.offset[x] + c]; break;
             case kSrcChannel: v = p[c]; break;
             case kSrcSquareChannel: v = p[(size_t)(row % 81) * a.C + c]; break;
+            case kSrcRankLine: // one value per rank, broadcast over its files
+                v = p[(size_t)((row / 81) * a.bufLines[x] + a.line0[x] + (int)(row % 81) / 9) * a.stride[x] + a.offset[x] + c];
+                break;
+            case kSrcFileLine: // one value per file, broadcast over its ranks
+                v = p[(size_t)((row / 81) * a.bufLines[x] + a.line0[x] + (int)(row % 81) % 9) * a.stride[x] + a.offset[x] + c];
+                break;
+            case kSrcLine: // a view of outLines of the buffer's lines
+                v = p[(size_t)((row / a.outLines) * a.bufLines[x] + a.line0[x] + (int)(row % a.outLines)) * a.stride[x] + a.offset[x] + c];
+                break;
             default: v = a.scalar[x]; break;
             }
             break;
@@ -138,6 +147,11 @@ __global__ __launch_bounds__(kThreads) void graphOutputs(DevView pol, int polSpa
 
 hipError_t launchGraphElt(const EltArgs& a, hipStream_t stream) {
     if (a.rows <= 0 || a.ncode <= 0 || a.ncode > kMaxEltCode) return hipErrorInvalidValue;
+    for (int i = 0; i < kMaxEltSrcs; ++i) {
+        const bool line = a.mode[i] == kSrcRankLine || a.mode[i] == kSrcFileLine || a.mode[i] == kSrcLine;
+        const int lines = a.mode[i] == kSrcLine ? a.outLines : 9;
+        if (line && (a.line0[i] < 0 || lines <= 0 || a.line0[i] + lines > a.bufLines[i])) return hipErrorInvalidValue;
+    }
     hipLaunchKernelGGL(graphElt, dim3(blocksFor(a.rows * a.outStride)), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }

@@ -868,7 +868,7 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
         d.p = ptr(v); d.stride = v.stride; d.offset = v.offset; d.C = v.C;
         return d;
     };
-    auto rowsOf = [&](const gr::View& v) -> long { return v.spatial ? (long)B * 81 : (long)B; };
+    auto rowsOf = [&](const gr::View& v) -> long { return v.spatial ? (long)B * 81 : v.lines ? (long)B * v.lines : (long)B; };
     const bool prof = ev->profile;
     if (prof && ev->evUsed + 4 > (int)ev->ev.size()) {
         int rc = drainProfile(ev);
@@ -918,7 +918,10 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
                 a.scalar[i] = S.scalar;
                 if (S.mode == gr::kSrcChannel || S.mode == gr::kSrcSquareChannel) a.src[i] = wts + S.constOff;
                 else if (S.mode != gr::kSrcScalar) { a.src[i] = ptr(S.v); a.stride[i] = S.v.stride; a.offset[i] = S.v.offset; }
+                a.bufLines[i] = S.v.bufLines;
+                a.line0[i] = S.v.line0;
             }
+            a.outLines = L.out.lines;
             for (size_t i = 0; i < L.code.size(); ++i)
                 a.code[i] = (uint32_t)L.code[i].op | (uint32_t)L.code[i].dst << 8 | (uint32_t)L.code[i].a << 16 | (uint32_t)L.code[i].b << 24;
             a.ncode = (int)L.code.size();
@@ -938,6 +941,10 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
             break;
         case gr::kLaunchPool:
             NSG_HIP(gr::launchGraphPool(dv(L.in), ptr(L.out), L.out.stride, L.kh, L.kw, L.dh, L.dw, L.poolMode, B, s));
+            break;
+        case gr::kLaunchLinePool:
+            NSG_HIP(gr::launchGraphLinePool(dv(L.in), ptr(L.out), L.out.stride, L.out.bufLines, L.out.line0, L.lineFiles,
+                                            L.poolMode, B, s));
             break;
         case gr::kLaunchConcat: {
             gr::ConcatArgs a{};

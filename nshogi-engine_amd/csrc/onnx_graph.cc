@@ -118,6 +118,9 @@ void Planner::lower(const Node& N, size_t K) {
     if (Op == "Shape" || !AnyRuntime) return hostFold(N);
     const Val& X = get(N, 0);
     double PowOne = 0;
+    // a line tensor is read by the ops of planner_lines.cc only
+    for (const std::string& I : N.In)
+        if (!I.empty() && Vals.at(I).runtime && Vals.at(I).form == kFormLine) return lineOp(N, K);
     if (formView(N) || attentionOp(N) || normOp(N, K)) return;
     if (bmmOperands(N)) return bmm(N, K);
     // [N,C,81] and the 4-D tensors exist only inside the patterns the calls above follow
@@ -188,6 +191,8 @@ void Planner::checkOutputs() {
         auto It = Vals.find(O);
         if (It == Vals.end()) outFail(O, "is never computed");
         if (!It->second.runtime) outFail(O, "is a constant");
+        if (It->second.form == kFormLine)
+            outFail(O, "is a line tensor " + dimsStr(It->second.dims) + ": it exists only between the rank / file pooling and the broadcast back onto the board (DESIGN.md section 13.3)");
         ready(O);
     }
     {
@@ -240,7 +245,8 @@ void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::
         Phys[(size_t)V] = Best;
     };
     for (int I = 0; I < NL; ++I) {
-        take(P.launches[(size_t)I].out.buf);
+        // (the two poolings of an 18-line block write one virtual buffer: it is taken once)
+        if (Phys[(size_t)P.launches[(size_t)I].out.buf] < 0) take(P.launches[(size_t)I].out.buf);
         for (size_t V = 0; V < NV; ++V)
             if (Last[V] == I && Phys[V] >= 0) Free[(size_t)Phys[V]] = true;
     }

@@ -8,8 +8,11 @@
 //                                  81 squares is the spatial layout, so flatten(2).transpose(1,2) costs no launch
 //   flat [N,C] / [N,C,1,1] / [N] -> [row = board][stride] floats
 //   head rows [N,H,K]           -> [row = board * H + head][stride] floats, a view of a flat [N,H*K] (K a multiple of 16)
+//   lines [N,C,9,1] / [N,C,1,9] / [N,C,18,1] -> [row = board * L + line][stride] floats, L = 9 or 18 lines per board: one
+//                                  value per rank (or per file) and channel, in a flat buffer of stride L * stride
 // stride = C rounded up to 16 (the conv kernel's K chunk); channels C..stride-1 are written as zero by every kernel.
-// A view names a buffer plus a channel offset, so `Slice` and `Split` along the channel axis cost no launch.
+// A view names a buffer plus a channel offset, so `Slice` and `Split` along the channel axis cost no launch; a view of a
+// line tensor names a first line as well, so the two halves of an 18-line block are views too.
 #ifndef NSG_ONNX_GRAPH_H
 #define NSG_ONNX_GRAPH_H
 
@@ -46,6 +49,9 @@ struct View {
     int offset = 0;  // first channel inside the row
     int C = 0;       // channels (a flat tensor: its width)
     bool spatial = false;
+    // a line tensor (lines > 0): `lines` rows per board starting at row `line0` of the `bufLines` rows the buffer holds
+    // per board; row (board, l) of the view is row board * bufLines + line0 + l of the buffer
+    int lines = 0, bufLines = 0, line0 = 0;
 };
 
 // Elementwise program: registers r0..r15; opcodes below.  LOAD reads source `a` into register `dst`.
@@ -64,6 +70,10 @@ enum EltMode {
     kSrcChannel,    // constant per channel: weights[constOff + c]
     kSrcScalar,     // constant: `scalar`
     kSrcSquareChannel, // constant per (square, channel), a learned positional embedding: weights[constOff + (row % 81) * C + c]
+    // line views (View::lines > 0), row = board * bufLines + line0 + l
+    kSrcRankLine,   // broadcast over the files of a spatial output: l = (row % 81) / 9
+    kSrcFileLine,   // broadcast over the ranks of a spatial output: l = (row % 81) % 9
+    kSrcLine,       // a line output reading a line view of as many lines: l = row % lines (kSrcSame when the view is its whole buffer)
 };
 struct EltSrc {
     int mode = kSrcScalar;
@@ -74,7 +84,7 @@ struct EltSrc {
 
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
-    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm
+    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool
 };
 // kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
@@ -108,6 +118,10 @@ struct Launch {
     // kLaunchPool: `in` (a spatial view at any channel offset) -> out, kh x kw taps at dilations dh, dw under the conv's
     // halo rule, stride 1: the board stays 9x9
     int poolMode = kPoolMax;
+    // kLaunchLinePool: `in` (a spatial view at any channel offset) -> out, a 9-line view: the max (kPoolMax) or the mean
+    // (kPoolAvgInclude) of each rank over its files (lineFiles false, [N,C,9,1]) or of each file over its ranks (true,
+    // [N,C,1,9]).  out.line0 / out.bufLines place the nine lines inside an 18-line block.
+    bool lineFiles = false;
     // kLaunchLayerNorm: over the channels of each row of `in` (token rows or boards); gamma at wOff, beta at biasOff
     float eps = 0.f;
     // kLaunchGroupNorm: `in` (a spatial view at any channel offset) normalised per (board, group of C / groups consecutive
@@ -130,7 +144,8 @@ struct Launch {
     float rtScale = 1.f;
     bool hasRtBias = false;
     // kLaunchConv, dense: the rows of a board.  1: flat [N,K]; H: head rows [N,H,K], rows of (board, head) at stride
-    // in.stride, H of them contiguous per board (the virtual buffer is flat with stride H * in.stride).
+    // in.stride, H of them contiguous per board (the virtual buffer is flat with stride H * in.stride); L: a line
+    // tensor's (board, line) rows, a 1x1 conv over them.
     int rowsPerBoard = 1;
     // kLaunchBmm: the product of two run-time token tensors per board, out = act(scale * sum), the sum first, then the
     // scalar, then `act` (a parameter-free Act).  A = `in`, B = `bmmB`, both token views at offsets that are multiples of 4.

@@ -26,6 +26,7 @@ uint64_t hashFloats(const std::vector<float>& W, size_t Begin, size_t End) { // 
 
 void view(const char* Name, const View& V) {
     std::printf(" %s=%d/%d/%d/%d/%c", Name, V.buf, V.stride, V.offset, V.C, V.spatial ? 's' : 'f');
+    if (V.lines) std::printf("/L%d@%d/%d", V.lines, V.line0, V.bufLines); // a line view: lines @ first line / lines of the buffer
 }
 
 // the offsets into `weights` a launch reads its constants at
@@ -76,6 +77,7 @@ void dump(const GraphPlan& P) {
             std::printf(" rtHeadStride=%d rtScale=%a", L.rtHeadStride, (double)L.rtScale);
         }
         if (L.rowsPerBoard != 1) std::printf(" rowsPerBoard=%d", L.rowsPerBoard);
+        if (L.kind == kLaunchLinePool) std::printf(" lineFiles=%d", L.lineFiles);
         if (L.kind == kLaunchBmm) { // A is `in`; scale and act are printed above
             view("bmmB", L.bmmB);
             std::printf(" bmmNN=%d bmmK=%d", L.bmmNN, L.bmmK);

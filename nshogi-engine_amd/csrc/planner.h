@@ -48,6 +48,7 @@ enum Form {
     kFormChanLast, // [N,9,9,C]: the spatial rows once more, for a LayerNorm over the channels between two Transposes
     kFormHeadRows, // [N,H,K]: rows of (board, head), a view of a flat [N,H*K]; read by a MatMul with a constant [K,M] only
     kFormScoreBias, // [N,H,81,81] or [N,1,81,81]: a flat or head-row tensor as the run-time bias of attention scores
+    kFormLine,      // [N,C,9,1] rank lines, [N,C,1,9] file lines, [N,C,18,1]: rows of (board, line); read by the ops of planner_lines.cc only
 };
 inline bool isAttForm(int F) { return F >= kFormTok4 && F <= kFormTokOut4; }
 
@@ -74,6 +75,7 @@ struct Val {
     int rtHead = 0;
     double rtScale = 1.0;
     int headRows = 0;           // kFormHeadRows: H; v.stride is the stride of one (board, head) row, v.C = K
+    int lineLaunch = -1;        // kFormLine: the kLaunchLinePool that wrote it and has no other reader yet (-1: none)
     std::string chain;          // names of the nodes absorbed so far
     // the GroupNorm pattern's state ([N,G,M] behind its InstanceNormalization, until the Reshape back)
     int normG = 0;              // > 0: normalised per group, not yet launched
@@ -89,6 +91,7 @@ struct Val {
 struct Group {
     bool open = true;
     bool spatial = false;
+    int lines = 0;    // > 0: a line tensor of that many lines per board
     int C = 0;
     std::vector<EltSrc> srcs;
     std::vector<EltInstr> code;
@@ -121,7 +124,7 @@ template <class Fn> void forEachView(Launch& L, Fn F) {
     F(L.rtBias);
     F(L.bmmB);
     for (EltSrc& S : L.srcs)
-        if (S.mode == kSrcSame || S.mode == kSrcBoard) F(S.v);
+        if (S.mode == kSrcSame || S.mode == kSrcBoard || S.mode >= kSrcRankLine) F(S.v);
     for (CopySeg& S : L.segs) F(S.v);
     F(L.out);
 }
@@ -190,6 +193,20 @@ class Planner {
         VirtAlsoFlat.push_back(0);
         return (int)VirtStride.size() - 1;
     }
+    // a line tensor of L lines per board in a buffer of its own: flat, L rows of the stride per board
+    View freshLines(int C, int L) {
+        View V;
+        V.stride = roundUp(std::max(C, 1), kChunk);
+        V.C = C;
+        V.lines = V.bufLines = L;
+        V.buf = newVirt(L * V.stride, false);
+        return V;
+    }
+    static int lineCount(const std::vector<int64_t>& D) { // 9 or 18 for the dims of a line tensor, else 0
+        if (D.size() != 4 || D[0] != kBatch || D[1] <= 0) return 0;
+        if (D[3] == 1 && (D[2] == 9 || D[2] == 18)) return (int)D[2];
+        return D[2] == 1 && D[3] == 9 ? 9 : 0;
+    }
     View freshView(int C, bool Spatial) {
         View V;
         V.stride = roundUp(std::max(C, 1), kChunk);
@@ -247,7 +264,7 @@ class Planner {
         Launch L;
         L.kind = kLaunchElt;
         L.name = Gr.name;
-        L.out = freshView(Gr.C, Gr.spatial);
+        L.out = Gr.lines ? freshLines(Gr.C, Gr.lines) : freshView(Gr.C, Gr.spatial);
         L.srcs = Gr.srcs;
         L.code = Gr.code;
         L.eltOut = Gr.outReg;
@@ -325,6 +342,11 @@ class Planner {
     // planner_pool.cc
     void pool(const Node& N);
     void reduceSquares(const Node& N);
+    // planner_lines.cc: rank and file pooling and the ops that read a line tensor
+    void linePool(const Node& N, bool Files, bool Max);
+    void lineOp(const Node& N, size_t Index);
+    void lineConv(const Node& N, size_t Index);
+    View linePlain(const std::string& Name, const std::string& Why);
     // planner_views.cc
     std::vector<int64_t> reshapeTarget(const Node& N, const std::vector<int64_t>& SD);
     bool formView(const Node& N);   // Transpose, and Reshape / Flatten to or from the forms above

@@ -10,6 +10,7 @@ struct EltBuilder {
     std::vector<std::vector<int64_t>> InDims;
     std::vector<int64_t> D; // the result's dims
     bool Tok = false, Spatial = false;
+    int Lines = 0; // > 0: the result is a line tensor of that many lines per board
     int C = 0, ChanAxis = 1;
     size_t Arity = 1;
     // what the node adds to the program behind its operands, beyond one instruction and one register: set by budget()
@@ -77,6 +78,9 @@ int EltBuilder::constOperand(size_t K, const Val& V) {
         S.constOff = Pl.addConst(F);
         return load(S);
     }
+    if (Lines)
+        fail("constant of shape " + dimsStr(InDims[K]) + " on the line tensor " + dimsStr(D) +
+             ": a per-(line, channel) constant is not supported on a line tensor (per-channel and scalar constants only)");
     fail("constant of shape " + dimsStr(InDims[K]) + " broadcast to " + dimsStr(D) +
          " (per-channel, per-(square, channel) and scalar constants only)");
 }
@@ -88,12 +92,28 @@ int EltBuilder::operand(size_t K) {
     if (!V.runtime) return constOperand(K, V);
     // runtime operand: how it varies relative to the output
     const std::vector<int64_t>& Di = InDims[K];
-    const bool Same = Tok ? (V.form == kFormToken && Di == D) : (Di == D || (Planner::flatC(Di) == C && !Spatial && Planner::flatC(D) == C));
-    const bool Board = !Tok && Spatial && !V.flatOfSpatial && Planner::flatC(Di) == C && Di.size() == 4;
-    if (!Same && !Board) fail("operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
+    const bool VLine = V.form == kFormLine;
+    bool Same, Board = false;
+    int Map = kSrcSame; // what a kSrcSame source of an inlined group becomes, and how the operand itself is loaded
+    if (Lines || VLine) {
+        // a line operand: of a line result with the same lines, or broadcast back onto the board
+        if (Lines && !VLine && !V.flatOfSpatial && Planner::flatC(Di) >= 0)
+            fail("a flat operand " + dimsStr(Di) + " ('" + Name + "') in a chain of line tensors " + dimsStr(D) +
+                 ": a per-board value is broadcast over the 81 squares of a board only, not over its lines");
+        Same = Lines && VLine && Di == D;
+        const bool Back = Spatial && VLine && V.v.lines == 9 && Di[1] == C;
+        if (!Same && !Back) fail("operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
+        if (Back) Map = Di[3] == 1 ? kSrcRankLine : kSrcFileLine;
+    } else {
+        Same = Tok ? (V.form == kFormToken && Di == D) : (Di == D || (Planner::flatC(Di) == C && !Spatial && Planner::flatC(D) == C));
+        Board = !Tok && Spatial && !V.flatOfSpatial && Planner::flatC(Di) == C && Di.size() == 4;
+        if (!Same && !Board) fail("operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
+        if (Board) Map = kSrcBoard;
+    }
     // an open group used only here: inline its program
     const Group* Open = V.group >= 0 ? &Pl.Groups[(size_t)V.group] : nullptr;
-    const bool Domain = Open && !V.flatOfSpatial && Open->C == C && (Open->spatial == NG.spatial || (Board && !Open->spatial));
+    const bool Domain = Open && !V.flatOfSpatial && Open->C == C &&
+                        (VLine ? Open->lines == V.v.lines : !Open->lines && (Open->spatial == NG.spatial || (Board && !Open->spatial)));
     if (Domain && Pl.absorbable(Name)) {
         Group& Gr = Pl.Groups[(size_t)V.group];
         // inline it only if the rest of the node still fits behind it: every operand still to come takes at least
@@ -105,7 +125,7 @@ int EltBuilder::operand(size_t K) {
             NG.nregs + Gr.nregs + (int)Rest + 1 + XRegs <= kMaxEltRegs) {
             const int RB = NG.nregs, SB = (int)NG.srcs.size();
             for (EltSrc S : Gr.srcs) {
-                if (Board && S.mode == kSrcSame) S.mode = kSrcBoard;
+                if (Map != kSrcSame && (S.mode == kSrcSame || S.mode == kSrcLine)) S.mode = Map;
                 NG.srcs.push_back(S);
             }
             for (EltInstr I : Gr.code) {
@@ -126,7 +146,8 @@ int EltBuilder::operand(size_t K) {
     }
     EltSrc S;
     S.v = V.flatOfSpatial ? Pl.plain(Name, N.Name + " (flatten)") : Pl.ready(Name).v;
-    S.mode = Board ? kSrcBoard : kSrcSame;
+    // (a line view that is not its whole buffer, one half of an 18-line block, is read through its line fields)
+    S.mode = Map != kSrcSame ? Map : VLine && (S.v.line0 != 0 || S.v.bufLines != S.v.lines) ? kSrcLine : kSrcSame;
     return load(S);
 }
 
@@ -231,18 +252,45 @@ void Planner::elementwise(const Node& N) {
     for (size_t K = 0; K < B.Arity; ++K) B.Tok = B.Tok || (get(N, K).runtime && get(N, K).form == kFormToken); // a token operand makes the result a token tensor
     if (B.Tok && !isTokenDims(D)) fail(N, "a token tensor broadcast to " + dimsStr(D));
     B.Spatial = isSpatialDims(D);
-    const int C = B.C = B.Tok ? (int)D[2] : B.Spatial ? (int)D[1] : flatC(D);
+    // line operands: the result is a line tensor of the same lines, or (broadcast back) a spatial tensor
+    const Val* Rank = nullptr;
+    const Val* File = nullptr;
+    bool AnyLine = false;
+    for (size_t K = 0; K < B.Arity; ++K) {
+        const Val& V = get(N, K);
+        if (!V.runtime || V.form != kFormLine) continue;
+        AnyLine = true;
+        (V.dims[2] == 1 ? File : Rank) = &V;
+    }
+    if (Rank && File)
+        fail(N, "rank lines " + dimsStr(Rank->dims) + " and file lines " + dimsStr(File->dims) + " in one " + Op +
+                    ": the two orientations meet only through Transpose [0,1,3,2] or on the board, each broadcast onto [N,C,9,9]");
+    if (AnyLine && !B.Spatial) {
+        B.Lines = lineCount(D);
+        if (!B.Lines) fail(N, "a line tensor broadcast to " + dimsStr(D));
+    }
+    const int C = B.C = B.Tok ? (int)D[2] : B.Spatial || B.Lines ? (int)D[1] : flatC(D);
     if (C < 0) fail(N, "output shape " + dimsStr(D) + " is neither [N,C,9,9], a token tensor nor flat");
     B.ChanAxis = B.Tok ? 2 : 1;
     Group& NG = B.NG;
     NG.spatial = B.Spatial || B.Tok;
+    NG.lines = B.Lines;
     NG.C = C;
     NG.name = N.Name;
     NG.out = N.Out[0];
     NG.outReg = B.expand(ActCode, PowE);
     if (NG.nregs > kMaxEltRegs || NG.code.size() > (size_t)kMaxEltCode) fail(N, "elementwise chain too long for one launch");
     Groups.push_back(NG);
-    Val V = runtimeVal(N, D, B.Tok ? kFormToken : kFormPlain);
+    Val V;
+    if (B.Lines) {
+        V.runtime = true;
+        V.dims = D;
+        V.producer = N.Name;
+        V.form = kFormLine;
+        V.v.lines = V.v.bufLines = B.Lines;
+    } else {
+        V = runtimeVal(N, D, B.Tok ? kFormToken : kFormPlain);
+    }
     V.group = (int)Groups.size() - 1;
     V.v.buf = kPending;
     V.v.C = C;

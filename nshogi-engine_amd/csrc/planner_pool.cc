@@ -34,6 +34,15 @@ void Planner::pool(const Node& N) {
         Vals[N.Out[0]] = V;
         return;
     }
+    // a window that is exactly one rank or one file, unpadded (what the exporter writes for adaptive_*_pool2d(x, (9, 1))
+    // and (1, 9)): the output is [N,C,9,1] or [N,C,1,9], a line tensor.  The stride along the window does not matter.
+    {
+        const bool Rank = Ks == std::vector<int64_t>{1, 9}, File = Ks == std::vector<int64_t>{9, 1};
+        const std::vector<int64_t> St = N.attrInts("strides", {1, 1});
+        if ((Rank || File) && Pads == std::vector<int64_t>{0, 0, 0, 0} && Dil == std::vector<int64_t>{1, 1} && !Ceil && !AutoPad &&
+            St.size() == 2 && St[Rank ? 0 : 1] == 1 && St[Rank ? 1 : 0] >= 1)
+            return linePool(N, File, Max);
+    }
     for (int64_t S : N.attrInts("strides", {1, 1}))
         if (S != 1) fail(N, "stride " + std::to_string(S) + ": only stride 1 (the output stays 9x9)");
     if (Ks[0] < 1 || Ks[1] < 1 || Ks[0] > 9 || Ks[1] > 9 || Ks[0] % 2 == 0 || Ks[1] % 2 == 0)
@@ -78,6 +87,12 @@ void Planner::reduceSquares(const Node& N) {
     if (Reduce) {
         std::vector<int64_t> Axes = axes(N, Tok ? 3 : 4);
         std::sort(Axes.begin(), Axes.end());
+        // along one board axis: over the files (axis 3) one value per rank, over the ranks (axis 2) one per file
+        if (!Tok && (Axes == std::vector<int64_t>{2} || Axes == std::vector<int64_t>{3})) {
+            if (N.attrI("keepdims", 1) == 0)
+                fail(N, Op + " over axis " + std::to_string(Axes[0]) + " of " + dimsStr(X.dims) + " with keepdims = 0: [N,C,9] is ambiguous with the other 3-D shapes; rank and file pooling keeps the axis (keepdims = 1)");
+            return linePool(N, Axes[0] == 2, Op == "ReduceMax");
+        }
         if (Tok ? Axes != std::vector<int64_t>{1} : Axes != std::vector<int64_t>{2, 3})
             fail(N, Op + " over the squares only: axes {2,3} of [N,C,9,9], axis 1 of a token tensor");
         Keep = N.attrI("keepdims", 1) != 0;
