@@ -900,6 +900,10 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
             if (L.depthwise)
                 NSG_HIP(gr::launchGraphDepthwise(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out),
                                                  L.out.stride, L.out.C, L.kh, L.kw, L.dh, L.dw, B, L.act, s));
+            else if (L.groups > 1)
+                NSG_HIP(gr::launchGraphConvGrouped(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff,
+                                                   (const int*)(wts + L.gTabOff), res, ptr(L.out), L.out.stride, L.out.C,
+                                                   L.kh, L.kw, L.dh, L.dw, B, L.act, s));
             else if (L.kh == L.kw && (L.kh == 1 || L.kh == 3) && L.dh == 1 && L.dw == 1)
                 NSG_HIP(gr::launchGraphConv(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out), L.out.stride,
                                             L.out.C, L.cinPad, L.coutTiles, L.taps, groups, L.dense ? denseRows : rowsOf(L.out),

@@ -31,6 +31,7 @@ constexpr int kMaxEltSrcs = 8;  // inputs of one fused elementwise launch
 constexpr int kMaxEltCode = 32; // instructions of one fused elementwise launch
 constexpr int kMaxEltRegs = 16;
 constexpr int kMaxCopySegs = 8; // sources of one channel concat
+constexpr int kGroupTabInts = 12; // ints per 64-output tile in a grouped conv's table (Launch::gTabOff)
 
 // kActGelu: exact (erf); kActRelu6 = min(max(x, 0), 6); kActHardSigmoid = min(max(x / 6 + 0.5, 0), 1); kActHardSwish =
 // x * that.  All of them are parameter-free: a LeakyRelu, a PRelu, other Clip bounds are elementwise instructions.
@@ -98,7 +99,8 @@ struct Launch {
     // kLaunchConv: an implicit-GEMM conv (taps = kh x kw, row-major over (ky, kx)), a dense layer (taps 1, rows =
     // boards) or a depthwise conv.  A tap reads the square (ky - (kh-1)/2) * dh rows and (kx - (kw-1)/2) * dw columns
     // away; the halo dh * (kh-1)/2 by dw * (kw-1)/2 is at most kMaxConvHalo each way.  1x1 and 3x3 at dilation 1 run
-    // on graphConv<1> / graphConv<9>, every other dense geometry on graphConvGeo, depthwise on graphDepthwise.
+    // on graphConv<1> / graphConv<9>, every other dense geometry on graphConvGeo, depthwise on graphDepthwise, a grouped
+    // conv (groups > 1, below) of any geometry on graphConvGrouped.
     View in, res;    // res.buf == -2: no residual
     bool dense = false;
     bool depthwise = false; // group = Cin = Cout: per-channel taps, no sum over channels
@@ -108,6 +110,13 @@ struct Launch {
     int coutTiles = 0;  // depthwise: unused (0)
     size_t wOff = 0;    // packed weights [coutTiles][cinPad / 16][taps][16][64]; depthwise: [cinPad / 16][taps][16]
     size_t biasOff = 0; // [coutTiles * 64]; depthwise: [cinPad]
+    // A grouped conv (1 < group < Cin, Cin / group a multiple of 4) is a kLaunchConv with `groups` > 1 (the field is
+    // shared with kLaunchGroupNorm, below).  Its packed weights are [tile][chunk of the tile's range][tap][16][64]: a
+    // tile of 64 outputs holds only the 16-channel input chunks that the groups of its outputs read, with exact zeros
+    // where input and output channel lie in different groups.  gTabOff: kGroupTabInts ints per tile, stored bit for
+    // bit in the float blob: first chunk, chunk count, the tile's weight offset in floats from wOff, 0, then
+    // (first chunk, chunk count) of each of the four waves' 16 outputs (a sub-range of the tile's; count 0: no output).
+    size_t gTabOff = 0;
     int act = kActNone;
     // kLaunchElt
     std::vector<EltSrc> srcs;

@@ -35,6 +35,7 @@ std::vector<size_t> constsOf(const Launch& L) {
     const int K = L.kind;
     if (K == kLaunchConv || K == kLaunchLayerNorm || K == kLaunchGroupNorm) R = {L.wOff, L.biasOff};
     if (K == kLaunchRmsNorm) R = {L.wOff};
+    if (K == kLaunchConv && L.groups > 1) R.push_back(L.gTabOff);
     if (K == kLaunchAttention && L.hasBias) R = {L.biasOff};
     for (const EltSrc& S : L.srcs)
         if (S.mode == kSrcChannel || S.mode == kSrcSquareChannel) R.push_back(S.constOff);
@@ -78,6 +79,7 @@ void dump(const GraphPlan& P) {
         }
         if (L.rowsPerBoard != 1) std::printf(" rowsPerBoard=%d", L.rowsPerBoard);
         if (L.kind == kLaunchLinePool) std::printf(" lineFiles=%d", L.lineFiles);
+        if (L.kind == kLaunchConv && L.groups > 1) std::printf(" gTabOff=%zu", L.gTabOff); // a grouped conv: groups is printed above
         if (L.kind == kLaunchBmm) { // A is `in`; scale and act are printed above
             view("bmmB", L.bmmB);
             std::printf(" bmmNN=%d bmmK=%d", L.bmmNN, L.bmmK);

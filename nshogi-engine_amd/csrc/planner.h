@@ -138,7 +138,8 @@ void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::
 // A linear layer's weights as read from the model, W[cout][CinW][taps], before packing (planner_linear.cc)
 struct LinearW {
     int Cin = 0, Cout = 0, KH = 1, KW = 1, DH = 1, DW = 1;
-    int CinW = 0;           // input channels per output channel in W: Cin, or 1 for a depthwise conv
+    int CinW = 0;           // input channels per output channel in W: Cin, Cin / Groups, or 1 for a depthwise conv
+    int Groups = 1;         // > 1: a grouped conv, output o reads the CinW inputs from (o / (Cout / Groups)) * CinW
     bool Depthwise = false;
     std::vector<double> W, Bias; // taps row-major over (ky, kx)
     int taps() const { return KH * KW; }

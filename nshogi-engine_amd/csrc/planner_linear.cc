@@ -1,6 +1,8 @@
 // planner_linear.cc -- the planner: Conv / Gemm / MatMul with their epilogue.
 #include "planner.h"
 
+#include <cstring>
+
 namespace nsg::graph {
 
 // A Conv's weights, bias and geometry, checked against the input X
@@ -37,11 +39,26 @@ LinearW Planner::convWeights(const Node& N, const Val& X) {
     const int64_t Group = N.attrI("group", 1);
     if (Group == 1) {
         L.Cin = (int)Wt.dims[1];
-    } else {
-        // depthwise only: group = Cin = Cout, weight [C,1,kh,kw]
+    } else if (Group != X.dims[1]) {
+        // a grouped conv: group divides Cin and Cout, weight [Cout,Cin/group,kh,kw], Cin/group a multiple of 4, so that
+        // an MFMA k-step and a 16-byte staged piece never straddle two groups
         const int64_t XC = X.dims[1];
-        if (Group != XC)
-            fail(N, "group " + std::to_string(Group) + " on " + std::to_string(XC) + " input channels: only group 1 or a depthwise conv (group = input channels = output channels)");
+        const std::string GStr = "group " + std::to_string(Group) + " on " + std::to_string(XC) + " input channels";
+        const std::string Or = " (or group 1, or a depthwise conv)";
+        if (Group < 1 || XC % Group != 0)
+            fail(N, GStr + ": the group count does not divide the input channels" + Or);
+        if (L.Cout % Group != 0)
+            fail(N, GStr + " and " + std::to_string(L.Cout) + " output channels: the group count does not divide the output channels" + Or);
+        const int64_t Per = XC / Group;
+        if (Wt.dims[1] != Per)
+            fail(N, GStr + " with a weight of " + std::to_string(Wt.dims[1]) + " channels per group: a grouped weight is [Cout," + std::to_string(Per) + ",kh,kw]");
+        if (Per % 4 != 0)
+            fail(N, GStr + " is " + std::to_string(Per) + " per group: a grouped conv needs a multiple of 4 input channels per group" + Or);
+        L.Groups = (int)Group;
+        L.Cin = (int)XC;
+    } else {
+        // depthwise: group = Cin = Cout, weight [C,1,kh,kw]
+        const int64_t XC = X.dims[1];
         if (Wt.dims[1] != 1) fail(N, "group " + std::to_string(Group) + " with a weight of " + std::to_string(Wt.dims[1]) + " channels per group: a depthwise weight is [C,1,kh,kw]");
         if (L.Cout != (int)XC)
             fail(N, "a depthwise conv with channel multiplier " + std::to_string(XC > 0 ? L.Cout / XC : 0) + " (" + std::to_string(XC) + " -> " +
@@ -51,7 +68,7 @@ LinearW Planner::convWeights(const Node& N, const Val& X) {
     }
     if ((int)X.dims[1] != L.Cin)
         fail(N, "the weight expects " + std::to_string(L.Cin) + " input channels, '" + N.In[0] + "' has " + std::to_string(X.dims[1]));
-    L.CinW = L.Depthwise ? 1 : L.Cin;
+    L.CinW = L.Depthwise ? 1 : L.Cin / L.Groups;
     if (Wt.f.size() != (size_t)L.Cout * L.CinW * L.KH * L.KW) fail(N, "the weight's data does not match its shape");
     L.W.assign(Wt.f.begin(), Wt.f.end());
     L.Bias.assign((size_t)L.Cout, 0.0);
@@ -164,6 +181,50 @@ static void packDense(const LinearW& L, int Chunks, int Tiles, std::vector<float
     for (int O = 0; O < L.Cout; ++O) (*Bf)[(size_t)O] = (float)L.Bias[(size_t)O];
 }
 
+// The grouped conv kernel's weights, tables and bias.  Output o belongs to group o / (Cout /
+// Groups) and reads the CinW input channels from group * CinW.  A tile of 64 outputs holds the 16-channel chunks its
+// outputs' groups read -- its chunk range -- as [chunk of the range][tap][16][64], exact zeros where input and output
+// channel lie in different groups; the tiles follow one another.  Tb: kGroupTabInts ints per tile, bit for bit in
+// floats: the range's first chunk and chunk count, the tile's offset into Pk in floats, 0, then (first chunk, chunk
+// count) of each wave's 16 outputs, a sub-range of the tile's (count 0: every output of the wave is past Cout).
+static void packGrouped(const LinearW& L, int Tiles, std::vector<float>* Pk, std::vector<float>* Tb, std::vector<float>* Bf) {
+    const int Taps = L.taps(), OutPer = L.Cout / L.Groups;
+    std::vector<int32_t> Tab((size_t)Tiles * kGroupTabInts, 0);
+    Pk->clear();
+    for (int T = 0; T < Tiles; ++T) {
+        int32_t* Row = &Tab[(size_t)T * kGroupTabInts];
+        int First = INT_MAX, End = 0;
+        for (int Wv = 0; Wv < kCoutTile / kChunk; ++Wv) {
+            const int OLo = T * kCoutTile + Wv * kChunk, OHi = std::min(OLo + kChunk, L.Cout) - 1; // the wave's outputs
+            if (OLo >= L.Cout) continue;
+            const int CLo = (OLo / OutPer) * L.CinW / kChunk, CHi = ((OHi / OutPer + 1) * L.CinW - 1) / kChunk;
+            Row[4 + 2 * Wv] = CLo;
+            Row[5 + 2 * Wv] = CHi - CLo + 1;
+            First = std::min(First, CLo);
+            End = std::max(End, CHi + 1);
+        }
+        const int Count = End - First;
+        const size_t Off = Pk->size();
+        Row[0] = First;
+        Row[1] = Count;
+        Row[2] = (int32_t)Off;
+        Pk->resize(Off + (size_t)Count * Taps * kChunk * kCoutTile, 0.f);
+        for (int Ch = 0; Ch < Count; ++Ch)
+            for (int Tp = 0; Tp < Taps; ++Tp)
+                for (int Kk = 0; Kk < kChunk; ++Kk)
+                    for (int Nn = 0; Nn < kCoutTile; ++Nn) {
+                        const int O = T * kCoutTile + Nn, I = (First + Ch) * kChunk + Kk;
+                        if (O >= L.Cout || I >= L.Cin || I / L.CinW != O / OutPer) continue;
+                        (*Pk)[Off + (((size_t)Ch * Taps + Tp) * kChunk + Kk) * kCoutTile + Nn] =
+                            (float)L.W[((size_t)O * L.CinW + I % L.CinW) * Taps + Tp];
+                    }
+    }
+    Tb->resize(Tab.size());
+    std::memcpy(Tb->data(), Tab.data(), Tab.size() * sizeof(int32_t));
+    Bf->assign((size_t)Tiles * kCoutTile, 0.f);
+    for (int O = 0; O < L.Cout; ++O) (*Bf)[(size_t)O] = (float)L.Bias[(size_t)O];
+}
+
 // The depthwise kernel's per-channel taps [chunk][tap][16] and bias [chunks * 16]
 static void packDepthwise(const LinearW& L, int Chunks, std::vector<float>* Pk, std::vector<float>* Bf) {
     const int Taps = L.taps();
@@ -204,11 +265,17 @@ void Planner::linear(const Node& N, size_t Index) {
     L.act = E.act;
     L.res.buf = kNoRes;
     if (!E.res.empty()) L.res = ready(E.res).v;
-    std::vector<float> Pk, Bf;
+    std::vector<float> Pk, Bf, Tb;
     if (Lw.Depthwise) packDepthwise(Lw, L.cinPad / kChunk, &Pk, &Bf);
+    else if (Lw.Groups > 1) packGrouped(Lw, L.coutTiles, &Pk, &Tb, &Bf);
     else packDense(Lw, L.cinPad / kChunk, L.coutTiles, &Pk, &Bf);
+    if (Pk.size() > (size_t)INT32_MAX) fail(N, "the packed weights exceed 2^31 floats");
     L.wOff = addConst(Pk);
     L.biasOff = addConst(Bf);
+    if (Lw.Groups > 1) { // the tables are constants of grouped launches only: every other plan keeps its blob
+        L.groups = Lw.Groups;
+        L.gTabOff = addConst(Tb);
+    }
     L.out = freshView(Cout, !L.dense);
     P.flopsPerPosition += 2.0 * (L.dense ? 1 : 81) * L.taps * (double)Lw.CinW * Cout;
     Val V = runtimeVal(N, Dims, OutForm);

@@ -16,6 +16,9 @@
     python scripts/graph_bench.py --smolgen [--out profiles/graph/smolgen_bench.json] [--repeats 3]   # the run-time bias row
     python scripts/graph_bench.py --trace-smolgen      # both transformers at B = 512 for `rocprofv3 --kernel-trace`
     python scripts/graph_bench.py --summarize-smolgen DIR/run_results.db   # graphAttention with and without the bias
+    python scripts/graph_bench.py --group [--out profiles/graph/group_bench.json] [--repeats 3]   # the grouped-conv row
+    python scripts/graph_bench.py --trace-group      # the ResNeXt net and its dense twin at B = 1, 32, 128, 512 for `rocprofv3 --kernel-trace`
+    python scripts/graph_bench.py --summarize-group DIR/run_results.db [--out profiles/graph/group_bench.json]
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
@@ -47,6 +50,13 @@ SmolgenPreNet: token Linear(256,32), flatten, Linear(2592,256) + swish, Linear(2
 Linear(64,6561), the Add into the scores), beside the plain --attention net, each timed `--repeats` times in turn.
 --trace-smolgen runs both at B = 512 in one process; --summarize-smolgen prints the median and range of every
 graphAttention instantiation (`<2, false>`: no run-time bias, `<2, true>`: with one) and of the head-row dense launch.
+
+--group: a ResNeXt-style 20x256 net (tests/group_models.py's ResNeXtNet: blocks of 1x1 -> 3x3 grouped, G = 8, 32 per
+group, with BatchNorm and ReLU -> 1x1, plus the residual), its twin with groups = 1 in the 3x3, and the forced family
+net, each timed `--repeats` times in turn at B = 1, 32, 128, 512.  --trace-group runs the two ResNeXt nets at those
+batches in one process (GROUP_FORWARDS forwards each); --summarize-group prints, per batch, the median and range of the
+grouped launch (graphConvGrouped) and of the twin's dense 3x3 256 -> 256 launch (graphConv<9>, the stem left out) and
+adds them to the --group file.
 """
 import argparse
 import importlib
@@ -142,6 +152,65 @@ def smolgen_onnx(path):
     import make_onnx_attention_golden as mk
     torch.manual_seed(16)
     mk.export_model(mk.randomize(abm.SmolgenPreNet(), 24).eval(), path)
+
+
+GROUP_BATCHES = (1, 32, 128, 512)
+GROUP_FORWARDS = 8  # --trace-group: 3 warm-up + 5 timed forwards per (net, batch)
+GROUP_BLOCKS = 20
+
+
+def group_onnx(path, groups):
+    """The ResNeXt-style 20x256 net; groups = 1 is the dense twin (the same seeds: every other layer is identical)."""
+    import torch
+    import group_models as gm
+    torch.manual_seed(14)
+    net = gm.randomize(gm.ResNeXtNet(F=256, groups=groups, blocks=GROUP_BLOCKS, swish=False, VC=32, VH=256), 22).eval()
+    gm.export(net, path)
+
+
+def summarize_group(db, out):
+    """A --trace-group run: the grouped net first, then the twin, each at GROUP_BATCHES in order, GROUP_FORWARDS forwards
+    of GROUP_BLOCKS 3x3 launches per batch (the twin's graphConv<9> launches one more per forward: the stem, left out)."""
+    import sqlite3
+    import statistics
+    c = sqlite3.connect(db)
+    print(f"{'kernel':60s} {'calls':>6s} {'total ms':>10s} {'avg us':>9s}")
+    for n, k, t, a in c.execute("select name, count(*), sum(end-start), avg(end-start) from kernels group by name "
+                                "order by sum(end-start) desc"):
+        short = n.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        print(f"{short:60s} {k:6d} {t / 1e6:10.2f} {a / 1e3:9.1f}")
+    print()
+    g = [r[0] for r in c.execute("select end-start from kernels where name like '%graphConvGrouped%' order by start")]
+    d = [r[0] for r in c.execute("select end-start from kernels where name like '%graphConv<9>%' order by start")]
+    per_g, per_d = GROUP_FORWARDS * GROUP_BLOCKS, GROUP_FORWARDS * (GROUP_BLOCKS + 1)
+    # graphConv<9>: the grouped net's own stems come first (one launch per forward), then the twin's stem + 20 per forward
+    d = d[GROUP_FORWARDS * len(GROUP_BATCHES):]
+    res = {}
+    for i, b in enumerate(GROUP_BATCHES):
+        gs = g[i * per_g:(i + 1) * per_g]
+        ds = [t for j, t in enumerate(d[i * per_d:(i + 1) * per_d]) if j % (GROUP_BLOCKS + 1) != 0]
+        # the warm-up forwards are left out of both
+        gs, ds = gs[3 * GROUP_BLOCKS:], ds[3 * GROUP_BLOCKS:]
+        if not gs or not ds:
+            continue
+        row = {}
+        for label, ts in (("grouped_3x3_g8", gs), ("dense_3x3", ds)):
+            row[label] = {"median_us": round(statistics.median(ts) / 1e3, 1), "min_us": round(min(ts) / 1e3, 1),
+                          "max_us": round(max(ts) / 1e3, 1), "launches": len(ts)}
+        row["dense_over_grouped"] = round(statistics.median(ds) / statistics.median(gs), 2)
+        res[str(b)] = row
+        print(f"B={b}: graphConvGrouped 3x3 256->256 G=8 median {row['grouped_3x3_g8']['median_us']} us (min "
+              f"{row['grouped_3x3_g8']['min_us']}, max {row['grouped_3x3_g8']['max_us']}, {len(gs)} launches); graphConv<9> dense "
+              f"3x3 256->256 median {row['dense_3x3']['median_us']} us (min {row['dense_3x3']['min_us']}, max "
+              f"{row['dense_3x3']['max_us']}, {len(ds)} launches); dense / grouped = {row['dense_over_grouped']}")
+    if out:
+        doc = {}
+        if os.path.exists(out):
+            with open(out) as f:
+                doc = json.load(f)
+        doc["trace_3x3_256_launch"] = res
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
 
 
 def summarize_smolgen(db):
@@ -342,7 +411,13 @@ def main():
     ap.add_argument("--smolgen", action="store_true", help="the transformer with a run-time attention bias per block, and without")
     ap.add_argument("--trace-smolgen", action="store_true", help="both at B=512, 13 forwards each")
     ap.add_argument("--summarize-smolgen", metavar="DB", help="graphAttention medians of a --trace-smolgen / --trace-attention run")
+    ap.add_argument("--group", action="store_true", help="the ResNeXt-style 20x256 net (G = 8), its dense twin and the forced family net")
+    ap.add_argument("--trace-group", action="store_true", help="the ResNeXt net and its twin at B = 1, 32, 128, 512, 8 forwards each")
+    ap.add_argument("--summarize-group", metavar="DB", help="grouped against dense 3x3 launch medians of a --trace-group run")
     a = ap.parse_args()
+    if a.summarize_group:
+        summarize_group(a.summarize_group, a.out.replace("graph_bench.json", "group_bench.json"))
+        return
     if a.summarize_smolgen:
         summarize_smolgen(a.summarize_smolgen)
         return
@@ -368,6 +443,39 @@ def main():
             make(path)
             r, info = rate(nsg, path, TRACE_BATCH, iters=POOL_FAMILY_FORWARDS - 3, warmup=3)
             print(json.dumps({label: r, "launches": info["launches"]}), flush=True)
+        return
+    if a.group or a.trace_group:
+        paths = {"resnext_20x256_g8_general": os.path.join(tmp, "resnext_g8.onnx"), "resnext_20x256_g1_general": os.path.join(tmp, "resnext_g1.onnx")}
+        group_onnx(paths["resnext_20x256_g8_general"], 8)
+        group_onnx(paths["resnext_20x256_g1_general"], 1)
+        if a.trace_group:
+            for k, path in paths.items():
+                for b in GROUP_BATCHES:
+                    r, info = rate(nsg, path, b, iters=GROUP_FORWARDS - 3, warmup=3)
+                    print(json.dumps({k: r, "batch": b, "launches": info["launches"]}), flush=True)
+            return
+        paths["family_20x256_general"] = os.path.join(tmp, "family.onnx")
+        family_onnx(nsg, paths["family_20x256_general"])
+        rows = {k: {} for k in paths}
+        batches = GROUP_BATCHES if a.batches == "1,64,512" else [int(b) for b in a.batches.split(",")]
+        for b in batches:
+            for rep in range(a.repeats):  # the nets in turn, so that drift of the clock falls on all of them
+                for k, path in paths.items():
+                    r, info = rate(nsg, path, b, force=k.startswith("family"), iters=20 if b >= 128 else 50)
+                    rows[k].setdefault(str(b), []).append(round(r, 1))
+                    rows[k].update(path=info["path"], launches=info["launches"], conv_launches=info["conv_launches"],
+                                   flops_per_position=info["flops_per_position"])
+        for k, row in rows.items():
+            print(k, json.dumps(row), flush=True)
+        out = a.out.replace("graph_bench.json", "group_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        doc = {}
+        if os.path.exists(out):
+            with open(out) as f:
+                doc = json.load(f)
+        doc.update(repeats=a.repeats, rows=rows)
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
         return
     if a.smolgen or a.trace_smolgen:
         paths = {"smolgen_8x256_general": os.path.join(tmp, "smolgen.onnx"), "attention_8x256_general": os.path.join(tmp, "att.onnx")}
