@@ -131,7 +131,10 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    with constant scalar Mul / Div nodes and one activation behind it folded
  *    in (sigmoid or ReLU attention without a head split is two launches); a
  *    transposed first operand, flat or spatial operands and a Softmax on the
- *    result stay refused.  A general graph always runs in
+ *    result stay refused.  A Linear over the 81 squares (MatMul of [N,C,81]
+ *    with a constant [81,D], bias, one activation, optionally the MatMul back
+ *    with [D,81]; D <= 336: MLP-Mixer, ResMLP, gMLP) is one launch as well.
+ *    A general graph always runs in
  *    exact fp32, whatever nsg_set_precision asked for.
  * When both refuse, the load fails with NSG_E_FORMAT and a message giving both
  * reasons, the general path's naming the node (the reference's parser

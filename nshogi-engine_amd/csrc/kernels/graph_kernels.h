@@ -1,5 +1,5 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
-// graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip, graph_gconv.hip).
+// graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip, graph_gconv.hip, graph_tokenmix.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -153,6 +153,16 @@ hipError_t launchGraphBmmNT(DevView a, DevView b, float scale, int act, float* o
 // NN: p [boards*81][81], v [boards*81][M] -> out[n,i,c] = sum_j p[n,i,j] v[n,j,c], outStride = M rounded up to 16.
 hipError_t launchGraphBmmNN(DevView p, DevView v, float scale, int act, float* out, int outStride, int boards,
                             hipStream_t stream);
+
+// A Linear over the 81 squares of every channel, one stage or two in one launch (graph_tokenmix.hip): with Dp = D rounded
+// up to 16 and the constant record consts = W1^T [Dp][84], b1 [Dp], W2^T [96][Dp], b2 [96] (the last two for two stages
+// only; every pad zero),
+//   h[n,d,c] = act1(sum_s W1^T[d][s] in[n,s,c] + b1[d]),   out[n,j,c] = act2(sum_d W2^T[j][d] h[n,d,c] + b2[j])
+// and with one stage (D = 81) out = h.  `in`: a view at an offset that is a multiple of 4, of any width C >= 1; outStride =
+// C rounded up to 16, pad channels written as zeros.  Every sum is one f32 chain whose order depends on D only; h never
+// leaves the registers of the wave that computed it.
+hipError_t launchGraphTokenMix(DevView in, const float* consts, int D, int stages, int act1, int act2, float* out,
+                               int outStride, int boards, hipStream_t stream);
 
 // [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)
 hipError_t launchGraphFlatten(DevView in, float* out, int outStride, int boards, hipStream_t stream);

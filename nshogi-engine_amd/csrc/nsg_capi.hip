@@ -992,6 +992,10 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
             if (L.bmmNN) NSG_HIP(gr::launchGraphBmmNN(dv(L.in), dv(L.bmmB), L.scale, L.act, ptr(L.out), L.out.stride, B, s));
             else NSG_HIP(gr::launchGraphBmmNT(dv(L.in), dv(L.bmmB), L.scale, L.act, ptr(L.out), L.out.stride, B, s));
             break;
+        case gr::kLaunchTokenMix:
+            NSG_HIP(gr::launchGraphTokenMix(dv(L.in), wts + L.wOff, L.mixD, L.mixStages, L.act, L.mixAct2, ptr(L.out),
+                                            L.out.stride, B, s));
+            break;
         default:
             return fail(NSG_E_INVALID, "internal error: unknown launch kind %d in the graph plan", L.kind);
         }

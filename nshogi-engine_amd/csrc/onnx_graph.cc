@@ -104,6 +104,7 @@ void Planner::defineInput() {
 void Planner::lower(const Node& N, size_t K) {
     const std::string& Op = N.Op;
     if (N.Out.empty()) fail(N, "no output");
+    if (PendingMix.count(K)) return mixFlush(K); // the last node of a token-mixing pattern: its launch goes here
     if (Op == "Constant") {
         if (!Vals.count(N.Out[0])) fail(N, "unsupported Constant attribute (value tensor or value_float only)");
         return;
@@ -123,6 +124,7 @@ void Planner::lower(const Node& N, size_t K) {
         if (!I.empty() && Vals.at(I).runtime && Vals.at(I).form == kFormLine) return lineOp(N, K);
     if (formView(N) || attentionOp(N) || normOp(N, K)) return;
     if (bmmOperands(N)) return bmm(N, K);
+    if (mixEntry(N)) return tokenMix(N, K);
     // [N,C,81] and the 4-D tensors exist only inside the patterns the calls above follow
     for (size_t J = 0; J < N.In.size(); ++J) {
         if (N.In[J].empty()) continue;

@@ -32,6 +32,7 @@ constexpr int kMaxEltCode = 32; // instructions of one fused elementwise launch
 constexpr int kMaxEltRegs = 16;
 constexpr int kMaxCopySegs = 8; // sources of one channel concat
 constexpr int kGroupTabInts = 12; // ints per 64-output tile in a grouped conv's table (Launch::gTabOff)
+constexpr int kMaxMixHidden = 336; // hidden units of a token-mixing MLP: 21 fragments of 16 (an expansion of 4 x 81 = 324 fits)
 
 // kActGelu: exact (erf); kActRelu6 = min(max(x, 0), 6); kActHardSigmoid = min(max(x / 6 + 0.5, 0), 1); kActHardSwish =
 // x * that.  All of them are parameter-free: a LeakyRelu, a PRelu, other Clip bounds are elementwise instructions.
@@ -85,7 +86,7 @@ struct EltSrc {
 
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
-    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool
+    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool, kLaunchTokenMix
 };
 // kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
@@ -164,6 +165,14 @@ struct Launch {
     View bmmB;
     bool bmmNN = false;
     int bmmK = 0;
+    // kLaunchTokenMix: a Linear over the 81 squares of every channel of `in` (a spatial view of C channels at an offset
+    // that is a multiple of 4), one stage or two: out[n,j,c] = act2(sum_d W2[d][j] h[n,d,c] + b2[j]) with h[n,d,c] =
+    // act(sum_s W1[s][d] in[n,s,c] + b1[d]), mixD hidden units (mixStages 2); or out = h with mixD = 81 (mixStages 1).
+    // One constant record at wOff, with Dp = mixD rounded up to 16: W1 transposed [Dp][84], b1 [Dp], then for two
+    // stages W2 transposed [96][Dp] and b2 [96], every pad zero.  act, mixAct2: parameter-free Acts.
+    int mixD = 0;
+    int mixStages = 0;
+    int mixAct2 = kActNone;
 };
 
 struct GraphPlan {

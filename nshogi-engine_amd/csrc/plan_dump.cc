@@ -34,7 +34,7 @@ std::vector<size_t> constsOf(const Launch& L) {
     std::vector<size_t> R;
     const int K = L.kind;
     if (K == kLaunchConv || K == kLaunchLayerNorm || K == kLaunchGroupNorm) R = {L.wOff, L.biasOff};
-    if (K == kLaunchRmsNorm) R = {L.wOff};
+    if (K == kLaunchRmsNorm || K == kLaunchTokenMix) R = {L.wOff};
     if (K == kLaunchConv && L.groups > 1) R.push_back(L.gTabOff);
     if (K == kLaunchAttention && L.hasBias) R = {L.biasOff};
     for (const EltSrc& S : L.srcs)
@@ -84,6 +84,8 @@ void dump(const GraphPlan& P) {
             view("bmmB", L.bmmB);
             std::printf(" bmmNN=%d bmmK=%d", L.bmmNN, L.bmmK);
         }
+        if (L.kind == kLaunchTokenMix) // the input is `in`, the first stage's act is printed above, the record's hash below
+            std::printf(" mixD=%d mixStages=%d mixAct2=%d", L.mixD, L.mixStages, L.mixAct2);
         std::printf(" srcs=%zu", L.srcs.size());
         for (const EltSrc& S : L.srcs) {
             std::printf(" [mode=%d", S.mode);

@@ -31,7 +31,8 @@ inline std::string dimsStr(const std::vector<int64_t>& D) {
 }
 
 // Logical shapes a runtime tensor may have besides [N,C,9,9] and flat.  kFormToken is a full citizen (dense layers,
-// elementwise ops, LayerNorm, the mean over squares); [N,C,81] exists only between a Reshape and a Transpose; the
+// elementwise ops, LayerNorm, the mean over squares); [N,C,81] exists only between a Reshape and a Transpose, where
+// the token-mixing pattern (planner_mix.cc) may read and write it; the
 // 4-D forms exist only inside the attention pattern and become one kLaunchAttention.
 enum Form {
     kFormPlain = 0,
@@ -166,6 +167,8 @@ class Planner {
     std::vector<int> VirtStride;     // per produced tensor (virtual buffer)
     std::vector<bool> VirtSpatial;
     std::vector<int> VirtAlsoFlat;   // see assignBuffers
+    struct PendingLaunch { Launch L; std::string out; Val V; };
+    std::map<size_t, PendingLaunch> PendingMix; // a token-mixing launch waiting for its pattern's last node (planner_mix.cc)
 
     [[noreturn]] void fail(const Node& N, const std::string& Why) const {
         throw Error("node '" + N.Name + "' (" + N.Op + "): " + Why);
@@ -357,6 +360,10 @@ class Planner {
     void headRowsDense(const Node& N, size_t Index); // MatMul of head rows [N,H,K] with a constant [K,M]
     bool bmmOperands(const Node& N) const;           // a MatMul of two run-time tensors outside the other patterns
     void bmm(const Node& N, size_t Index);           // ... as one kLaunchBmm (planner_linear.cc)
+    // planner_mix.cc: a Linear over the 81 squares, one stage or two, as one kLaunchTokenMix
+    bool mixEntry(const Node& N) const;              // a MatMul of a run-time [N,C,81] tensor with a constant
+    void tokenMix(const Node& N, size_t Index);
+    void mixFlush(size_t Index);
     bool attentionOp(const Node& N); // MatMul / Mul / Div / Add / Softmax on the attention pattern's 4-D tensors
     void viewOp(const Node& N);     // Flatten / Reshape / Squeeze / Unsqueeze / Identity on a spatial or flat tensor
     void concat(const Node& N);
