@@ -134,6 +134,9 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    result stay refused.  A Linear over the 81 squares (MatMul of [N,C,81]
  *    with a constant [81,D], bias, one activation, optionally the MatMul back
  *    with [D,81]; D <= 336: MLP-Mixer, ResMLP, gMLP) is one launch as well.
+ *    A Gather of an activation with constant indices (o[:, 0], tok[:, 40],
+ *    x[:, IDX], logits[:, MAP]) and a Slice with step -1 over a whole board
+ *    axis (x.flip(2), x.flip(3)) are one launch each.
  *    A general graph always runs in
  *    exact fp32, whatever nsg_set_precision asked for.
  * When both refuse, the load fails with NSG_E_FORMAT and a message giving both

@@ -1,5 +1,6 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
-// graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip, graph_gconv.hip, graph_tokenmix.hip).
+// graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip, graph_gconv.hip, graph_tokenmix.hip,
+// graph_gather.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -163,6 +164,14 @@ hipError_t launchGraphBmmNN(DevView p, DevView v, float scale, int act, float* o
 // leaves the registers of the wave that computed it.
 hipError_t launchGraphTokenMix(DevView in, const float* consts, int D, int stages, int act1, int act2, float* out,
                                int outStride, int boards, hipStream_t stream);
+
+// A Gather with constant indices or a board flip (graph_gather.hip): per board, out[r][c] = src[board * blockFloats +
+// rowTab[r] + colTab[c]] for r < rowsPerBoard, c < C, zeros for C <= c < outStride.  rowTab[rowsPerBoard] and
+// colTab[outStride] (16-byte aligned, pad entries 0) are the planner's, which has checked that no entry is negative
+// and that max(rowTab) + max(colTab) < blockFloats: the kernel reads nothing outside the board's block and checks
+// nothing itself.  outStride a multiple of 16.  The output holds the source's bits.
+hipError_t launchGraphGather(const float* src, long blockFloats, const int* rowTab, const int* colTab, float* out,
+                             int outStride, int C, int rowsPerBoard, int boards, hipStream_t stream);
 
 // [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)
 hipError_t launchGraphFlatten(DevView in, float* out, int outStride, int boards, hipStream_t stream);

@@ -996,6 +996,12 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
             NSG_HIP(gr::launchGraphTokenMix(dv(L.in), wts + L.wOff, L.mixD, L.mixStages, L.act, L.mixAct2, ptr(L.out),
                                             L.out.stride, B, s));
             break;
+        case gr::kLaunchGather: {
+            const int* tabs = (const int*)(wts + L.gatherTabOff); // rowTab, then colTab at the next multiple of 4 ints
+            NSG_HIP(gr::launchGraphGather(ptr(L.in), L.gatherBlock, tabs, tabs + (L.gatherRows + 3) / 4 * 4, ptr(L.out),
+                                          L.out.stride, L.out.C, L.gatherRows, B, s));
+            break;
+        }
         default:
             return fail(NSG_E_INVALID, "internal error: unknown launch kind %d in the graph plan", L.kind);
         }

@@ -162,6 +162,8 @@ void Planner::lower(const Node& N, size_t K) {
         split(N);
     } else if (Op == "GlobalAveragePool" || Op == "ReduceMean" || Op == "GlobalMaxPool" || Op == "ReduceMax") {
         reduceSquares(N);
+    } else if (Op == "Gather") {
+        gather(N);
     } else if (X.form == kFormToken && Op != "Slice" && Op != "Identity") { // (Split on tokens is taken above)
         fail(N, "op '" + Op + "' is not supported on a token tensor " + dimsStr(X.dims));
     } else if (Op == "Flatten" || Op == "Reshape" || Op == "Squeeze" || Op == "Unsqueeze" || Op == "Identity") {
@@ -170,7 +172,7 @@ void Planner::lower(const Node& N, size_t K) {
         concat(N);
     } else if (Op == "Slice") {
         slice(N);
-    } else if (Op == "Gather" || Op == "Cast") {
+    } else if (Op == "Cast") {
         fail(N, "applied to a runtime tensor (folded on shape values only)");
     } else {
         fail(N, "op '" + Op + "' is not supported on runtime tensors");

@@ -86,7 +86,7 @@ struct EltSrc {
 
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
-    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool, kLaunchTokenMix
+    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool, kLaunchTokenMix, kLaunchGather
 };
 // kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
@@ -173,6 +173,16 @@ struct Launch {
     int mixD = 0;
     int mixStages = 0;
     int mixAct2 = kActNone;
+    // kLaunchGather: a Gather with constant indices, or a board flip.  Per board the output has gatherRows rows (81: spatial
+    // or token rows; 1: a flat row) of out.stride floats, and the source is a block of gatherBlock floats (81 * in.stride for
+    // spatial or token rows, in.stride for a flat row) in `in`'s buffer.  Output element (r, c), c < out.C, is
+    // src[board * gatherBlock + rowTab[r] + colTab[c]] (in.offset is inside colTab); elements c >= out.C are zero.  The
+    // two int tables lie at gatherTabOff, stored bit for bit in the float blob as a grouped conv's table is: rowTab
+    // [gatherRows], then colTab[out.stride] with pad entries 0, each 16-byte aligned.  The planner checks every entry:
+    // max(rowTab) + max(colTab) < gatherBlock, none negative.  The device checks nothing.
+    int gatherRows = 0;
+    long gatherBlock = 0;
+    size_t gatherTabOff = 0;
 };
 
 struct GraphPlan {

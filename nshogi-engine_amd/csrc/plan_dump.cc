@@ -37,6 +37,7 @@ std::vector<size_t> constsOf(const Launch& L) {
     if (K == kLaunchRmsNorm || K == kLaunchTokenMix) R = {L.wOff};
     if (K == kLaunchConv && L.groups > 1) R.push_back(L.gTabOff);
     if (K == kLaunchAttention && L.hasBias) R = {L.biasOff};
+    if (K == kLaunchGather) R = {L.gatherTabOff};
     for (const EltSrc& S : L.srcs)
         if (S.mode == kSrcChannel || S.mode == kSrcSquareChannel) R.push_back(S.constOff);
     return R;
@@ -86,6 +87,8 @@ void dump(const GraphPlan& P) {
         }
         if (L.kind == kLaunchTokenMix) // the input is `in`, the first stage's act is printed above, the record's hash below
             std::printf(" mixD=%d mixStages=%d mixAct2=%d", L.mixD, L.mixStages, L.mixAct2);
+        if (L.kind == kLaunchGather) // the source is `in`; the width is out's stride; the two tables' hash is below
+            std::printf(" gatherRows=%d gatherBlock=%ld gatherWidth=%d gatherTabOff=%zu", L.gatherRows, L.gatherBlock, L.out.stride, L.gatherTabOff);
         std::printf(" srcs=%zu", L.srcs.size());
         for (const EltSrc& S : L.srcs) {
             std::printf(" [mode=%d", S.mode);

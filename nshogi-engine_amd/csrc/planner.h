@@ -364,6 +364,11 @@ class Planner {
     bool mixEntry(const Node& N) const;              // a MatMul of a run-time [N,C,81] tensor with a constant
     void tokenMix(const Node& N, size_t Index);
     void mixFlush(size_t Index);
+    // planner_gather.cc: Gather with constant indices and board flips, one kLaunchGather each
+    void gather(const Node& N);
+    void flipBoard(const Node& N, Val V, bool Ranks, bool Files); // a Slice with step -1 over whole board axes
+    View gatherLaunch(const Node& N, const View& In, long Block, const std::vector<int>& RowTab, const std::vector<int>& ColTab,
+                      bool Spatial);
     bool attentionOp(const Node& N); // MatMul / Mul / Div / Add / Softmax on the attention pattern's 4-D tensors
     void viewOp(const Node& N);     // Flatten / Reshape / Squeeze / Unsqueeze / Identity on a spatial or flat tensor
     void concat(const Node& N);

@@ -510,9 +510,10 @@ void Planner::concat(const Node& N) {
     Vals[N.Out[0]] = V;
 }
 
-// ---- Slice along the channels: a view
+// ---- Slice along the channels: a view.  With step -1 over a whole board axis: a flip, one launch (planner_gather.cc)
 void Planner::slice(const Node& N) {
-    const Val Src = get(N, 0).flatOfSpatial ? (plain(N.In[0], N.Name + " (flatten)"), Vals.at(N.In[0])) : ready(N.In[0]);
+    const bool WasFlat = get(N, 0).flatOfSpatial; // (the copy below makes it a flat tensor of its own)
+    const Val Src = WasFlat ? (plain(N.In[0], N.Name + " (flatten)"), Vals.at(N.In[0])) : ready(N.In[0]);
     const std::vector<int64_t> St = ints(N, 1, "starts"), En = ints(N, 2, "ends");
     std::vector<int64_t> Axes = has(N, 3) ? ints(N, 3, "axes") : std::vector<int64_t>();
     const std::vector<int64_t> Sp = has(N, 4) ? ints(N, 4, "steps") : std::vector<int64_t>(St.size(), 1);
@@ -521,8 +522,20 @@ void Planner::slice(const Node& N) {
     Val V = Src;
     V.producer = N.Name;
     const int64_t ChanAxis = Src.form == kFormToken ? 2 : 1;
+    // step -1 over a whole board axis of a spatial tensor (x.flip(2), x.flip(3)): the squares re-ordered, one launch
+    const bool Board = Src.form == kFormPlain && !WasFlat && isSpatialDims(Src.dims);
+    bool FlipRanks = false, FlipFiles = false;
     for (size_t J = 0; J < Axes.size(); ++J) {
         int64_t A = Axes[J] < 0 ? Axes[J] + (int64_t)Src.dims.size() : Axes[J];
+        if (Sp[J] == -1 && Board && (A == 2 || A == 3)) {
+            // ONNX: the start is clamped to [0, 8], the end to [-1, 8]; the whole axis runs from 8 down to and excluding -1
+            const int64_t S = std::max<int64_t>(0, std::min<int64_t>(St[J] < 0 ? St[J] + 9 : St[J], 8));
+            const int64_t E = std::max<int64_t>(-1, std::min<int64_t>(En[J] < 0 ? En[J] + 9 : En[J], 8));
+            if (S == 8 && E == -1 && !(A == 2 ? FlipRanks : FlipFiles)) {
+                (A == 2 ? FlipRanks : FlipFiles) = true;
+                continue;
+            }
+        }
         if (Sp[J] != 1) fail(N, "Slice with a step other than 1");
         if (A == ChanAxis) {
             const int64_t Len = Src.v.C;
@@ -538,6 +551,7 @@ void Planner::slice(const Node& N) {
             if (St[J] != 0 || (Dim != kBatch && En[J] < Dim)) fail(N, "Slice along an axis other than the channels");
         }
     }
+    if (FlipRanks || FlipFiles) return flipBoard(N, V, FlipRanks, FlipFiles);
     Vals[N.Out[0]] = V;
 }
 
