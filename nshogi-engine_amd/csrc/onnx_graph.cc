@@ -17,7 +17,7 @@ void Planner::run() {
     for (size_t K = 0; K < Nodes.size(); ++K)
         if (!Skip[K]) lower(Nodes[K], K);
     checkOutputs();
-    assignBuffers(P, VirtStride, VirtSpatial, VirtAlsoFlat);
+    assignBuffers(P, VirtStride, VirtSpatial, VirtAlsoFlat, Trace);
 }
 
 // tensor contract (trt.cc:144-227), and the op set
@@ -215,7 +215,7 @@ void Planner::checkOutputs() {
 
 // lifetimes -> physical buffers (a launch's output never shares a buffer with its inputs)
 void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::vector<bool>& VirtSpatial,
-                   const std::vector<int>& VirtAlsoFlat) {
+                   const std::vector<int>& VirtAlsoFlat, LifetimeTrace* Trace) {
     const size_t NV = VirtStride.size();
     const int NL = (int)P.launches.size();
     std::vector<int> Last(NV, -1); // the last launch that touches each virtual buffer (NL: a graph output)
@@ -258,8 +258,27 @@ void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::
         if (V.buf == kPending) throw Error("internal planner error: a launch reads an elementwise result before it is computed");
         if (V.buf >= 0) V.buf = Phys[(size_t)V.buf];
     };
-    for (Launch& L : P.launches) forEachView(L, rename);
-    for (View* V : {&P.policy, &P.value, &P.draw}) rename(*V);
+    // the renaming, and beside it the record of what was renamed (LifetimeTrace)
+    LifetimeTrace Unkept;
+    LifetimeTrace& T = Trace ? *Trace : Unkept;
+    T.virtStride = VirtStride;
+    T.virtSpatial = VirtSpatial;
+    T.virtAlsoFlat = VirtAlsoFlat;
+    T.virtPhys = Phys;
+    auto traced = [&](std::vector<ViewTrace>& Row, const char* Name, View& V) {
+        ViewTrace R;
+        R.field = Name;
+        R.virt = V.buf;
+        rename(V);
+        R.v = V;
+        Row.push_back(R);
+    };
+    T.launches.resize(P.launches.size());
+    for (size_t I = 0; I < P.launches.size(); ++I)
+        forEachNamedView(P.launches[I], [&](const char* Name, View& V) { traced(T.launches[I], Name, V); });
+    traced(T.outputs, "policy", P.policy);
+    traced(T.outputs, "value", P.value);
+    traced(T.outputs, "draw", P.draw);
     size_t Bytes = (size_t)P.planeStride * 81 * 4;
     for (size_t K = 0; K < P.bufSpatialStride.size(); ++K)
         Bytes += 4 * std::max((size_t)P.bufSpatialStride[K] * 81, (size_t)P.bufFlatStride[K]);
@@ -267,11 +286,17 @@ void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::
 }
 
 bool buildPlan(const void* Data, size_t Size, int NumChannels, GraphPlan* Plan, std::string* Err) {
+    return buildPlanTraced(Data, Size, NumChannels, Plan, nullptr, Err);
+}
+
+bool buildPlanTraced(const void* Data, size_t Size, int NumChannels, GraphPlan* Plan, LifetimeTrace* Trace, std::string* Err) {
     try {
         const Graph G = readModel(Span{(const unsigned char*)Data, Size});
         GraphPlan P;
         P.numChannels = NumChannels;
-        Planner(G, NumChannels, &P).run();
+        LifetimeTrace T;
+        Planner(G, NumChannels, &P, Trace ? &T : nullptr).run();
+        if (Trace) *Trace = std::move(T);
         *Plan = std::move(P);
         return true;
     } catch (const std::exception& E) {

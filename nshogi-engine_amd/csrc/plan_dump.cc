@@ -1,9 +1,13 @@
 // plan_dump.cc -- prints every field of the GraphPlan the planner returns for each model, as text: the planner's
 // output pinned on the CPU (tests/test_plan_snapshot.py compares it with tests/golden/graph_plans.txt).
-//   plan_dump [--planes N] MODEL.onnx ... [--planes M] MODEL.onnx ...     (N: the input planes, 86 until given)
-// Uses the public onnx_graph.h only.  Floats print as %a and doubles as %.17g, so every bit shows; no path beyond the
+//   plan_dump [--lifetimes] [--planes N] MODEL.onnx ... [--planes M] MODEL.onnx ...     (N: the input planes, 86 until given)
+// --lifetimes: after each plan, the virtual buffers the views had before assignBuffers renamed them (LifetimeTrace), for
+// tests/plan_check.py.  Without the flag the output is what it was before the flag existed.
+// Uses the public onnx_graph.h, and plan_lifetimes.h for --lifetimes.
+// Floats print as %a and doubles as %.17g, so every bit shows; no path beyond the
 // model's base name and no timing appears: two runs print the same bytes.
 #include "onnx_graph.h"
+#include "plan_lifetimes.h"
 
 #include <algorithm>
 #include <cinttypes>
@@ -117,11 +121,37 @@ void dump(const GraphPlan& P) {
     std::printf("\n");
 }
 
+// "V<id> stride spatial alsoFlat phys" per virtual buffer, then per launch every view of forEachView as
+// field:virtual followed by the renamed view
+void dumpLifetimes(const LifetimeTrace& T) {
+    std::printf("lifetimes virtuals=%zu\n", T.virtStride.size());
+    for (size_t V = 0; V < T.virtStride.size(); ++V)
+        std::printf("V%zu stride=%d spatial=%d alsoFlat=%d phys=%d\n", V, T.virtStride[V], (int)T.virtSpatial[V], T.virtAlsoFlat[V], T.virtPhys[V]);
+    auto row = [](const std::vector<ViewTrace>& Row) {
+        for (const ViewTrace& R : Row) {
+            std::printf(" %s:%d", R.field.c_str(), R.virt);
+            view("v", R.v);
+        }
+        std::printf("\n");
+    };
+    for (size_t I = 0; I < T.launches.size(); ++I) {
+        std::printf("L%zu", I);
+        row(T.launches[I]);
+    }
+    std::printf("LO");
+    row(T.outputs);
+}
+
 } // namespace
 
 int main(int Argc, char** Argv) {
     int Planes = 86;
+    bool Lifetimes = false;
     for (int A = 1; A < Argc; ++A) {
+        if (!std::strcmp(Argv[A], "--lifetimes")) {
+            Lifetimes = true;
+            continue;
+        }
         if (!std::strcmp(Argv[A], "--planes") && A + 1 < Argc) {
             Planes = std::atoi(Argv[++A]);
             continue;
@@ -136,8 +166,11 @@ int main(int Argc, char** Argv) {
         const std::string Data((std::istreambuf_iterator<char>(F)), std::istreambuf_iterator<char>());
         GraphPlan P;
         std::string Err;
-        if (buildPlan(Data.data(), Data.size(), Planes, &P, &Err)) dump(P);
-        else std::printf("ERROR %s\n", Err.c_str());
+        LifetimeTrace T;
+        if (buildPlanTraced(Data.data(), Data.size(), Planes, &P, Lifetimes ? &T : nullptr, &Err)) {
+            dump(P);
+            if (Lifetimes) dumpLifetimes(T);
+        } else std::printf("ERROR %s\n", Err.c_str());
     }
     return 0;
 }

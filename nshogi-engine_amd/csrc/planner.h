@@ -5,6 +5,7 @@
 
 #include "onnx_graph.h"
 #include "onnx_proto.h"
+#include "plan_lifetimes.h"
 
 #include <algorithm>
 #include <climits>
@@ -116,25 +117,30 @@ void rewritePatterns(std::vector<Node>& Nodes, std::vector<bool>& Skip, const st
                      const std::set<std::string>& Outputs);
 
 // Every device view a launch reads or writes: the lifetime pass and the renaming pass of assignBuffers go through it,
-// so a view field is named once.
-template <class Fn> void forEachView(Launch& L, Fn F) {
-    F(L.in);
-    F(L.res);
-    F(L.attK);
-    F(L.attV);
-    F(L.rtBias);
-    F(L.bmmB);
+// so a view field is named once.  F(Name, View&): the name is what the lifetimes dump prints (LifetimeTrace).
+template <class Fn> void forEachNamedView(Launch& L, Fn F) {
+    static const char* const SrcName[] = {"srcSame", "srcBoard", "", "", "", "srcRankLine", "srcFileLine", "srcLine"};
+    F("in", L.in);
+    F("res", L.res);
+    F("attK", L.attK);
+    F("attV", L.attV);
+    F("rtBias", L.rtBias);
+    F("bmmB", L.bmmB);
     for (EltSrc& S : L.srcs)
-        if (S.mode == kSrcSame || S.mode == kSrcBoard || S.mode >= kSrcRankLine) F(S.v);
-    for (CopySeg& S : L.segs) F(S.v);
-    F(L.out);
+        if (S.mode == kSrcSame || S.mode == kSrcBoard || S.mode >= kSrcRankLine) F(SrcName[S.mode], S.v);
+    for (CopySeg& S : L.segs) F("seg", S.v);
+    F("out", L.out);
+}
+template <class Fn> void forEachView(Launch& L, Fn F) {
+    forEachNamedView(L, [&](const char*, View& V) { F(V); });
 }
 
 // Lifetimes -> physical buffers: renames the virtual buffers of the launches' views and of the three output views,
 // and fills the plan's buffer stride tables (onnx_graph.cc).
 // VirtAlsoFlat: the flat stride a spatial virtual buffer is also read at (a token tensor viewed as flat rows), 0 = none.
+// Trace: where given, the record of what was renamed (plan_lifetimes.h).
 void assignBuffers(GraphPlan& P, const std::vector<int>& VirtStride, const std::vector<bool>& VirtSpatial,
-                   const std::vector<int>& VirtAlsoFlat);
+                   const std::vector<int>& VirtAlsoFlat, LifetimeTrace* Trace = nullptr);
 
 // A linear layer's weights as read from the model, W[cout][CinW][taps], before packing (planner_linear.cc)
 struct LinearW {
@@ -148,7 +154,8 @@ struct LinearW {
 
 class Planner {
  public:
-    Planner(const Graph& G, int NumChannels, GraphPlan* P) : G(G), P(*P), NumChannels(NumChannels) {}
+    Planner(const Graph& G, int NumChannels, GraphPlan* P, LifetimeTrace* Trace = nullptr)
+        : G(G), P(*P), NumChannels(NumChannels), Trace(Trace) {}
 
     void run();
 
@@ -156,6 +163,7 @@ class Planner {
     const Graph& G;
     GraphPlan& P;
     const int NumChannels;
+    LifetimeTrace* const Trace;
     std::map<std::string, Val> Vals;
     std::map<std::string, int> Uses; // live consumers (+1 for a graph output)
     std::map<std::string, int> ShapeUses; // ... of which Shape nodes
