@@ -1,6 +1,6 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
 // graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip, graph_gconv.hip, graph_tokenmix.hip,
-// graph_gather.hip).
+// graph_gather.hip, graph_chanreduce.hip).
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -60,7 +60,7 @@ struct EltArgs {
     const float* src[kMaxEltSrcs];
     int stride[kMaxEltSrcs];
     int offset[kMaxEltSrcs];
-    int mode[kMaxEltSrcs];  // EltMode; kSrcChannel and kSrcSquareChannel read constants at src
+    int mode[kMaxEltSrcs];  // EltMode; kSrcChannel, kSrcSquareChannel and kSrcSquare read constants at src
     int bufLines[kMaxEltSrcs], line0[kMaxEltSrcs]; // kSrcRankLine, kSrcFileLine, kSrcLine: the view's line fields
     float scalar[kMaxEltSrcs];
     uint32_t code[kMaxEltCode]; // op | dst << 8 | a << 16 | b << 24
@@ -172,6 +172,13 @@ hipError_t launchGraphTokenMix(DevView in, const float* consts, int D, int stage
 // nothing itself.  outStride a multiple of 16.  The output holds the source's bits.
 hipError_t launchGraphGather(const float* src, long blockFloats, const int* rowTab, const int* colTab, float* out,
                              int outStride, int C, int rowsPerBoard, int boards, hipStream_t stream);
+
+// The max (kRedMax), min (kRedMin) or sum (kRedSum) over the in.C channels of each of `rows` rows (graph_chanreduce.hip):
+// out[row][0] = the result, a sum multiplied by `scale` once after its last add; out[row][1 .. outStride-1] = 0.  `in`
+// may start at any channel of its rows (the ragged ends of an offset that is no multiple of 4 are read with scalar
+// loads); nothing outside [offset, offset + C) is read.  in.stride a multiple of 4, in.p 16-byte aligned.  The order of a
+// sum depends on (C, offset) only.  Max and min are fmaxf / fminf folds from -inf / +inf: a NaN element is skipped.
+hipError_t launchGraphChanReduce(DevView in, int mode, float scale, float* out, int outStride, long rows, hipStream_t stream);
 
 // [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)
 hipError_t launchGraphFlatten(DevView in, float* out, int outStride, int boards, hipStream_t stream);

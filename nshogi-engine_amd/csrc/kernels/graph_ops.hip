@@ -45,6 +45,9 @@ __global__ __launch_bounds__(kThreads) void graphElt(EltArgs a) {
             case kSrcLine: // a view of outLines of the buffer's lines
                 v = p[(size_t)((row / a.outLines) * a.bufLines[x] + a.line0[x] + (int)(row % a.outLines)) * a.stride[x] + a.offset[x] + c];
                 break;
+            case kSrcRowOne: v = p[(size_t)row * a.stride[x] + a.offset[x]]; break; // channel 0 of a one-channel view's row
+            case kSrcBoardOne: v = p[(size_t)(row / 81) * a.stride[x] + a.offset[x]]; break; // ... of its board's flat row
+            case kSrcSquare: v = p[row % 81]; break;
             default: v = a.scalar[x]; break;
             }
             break;

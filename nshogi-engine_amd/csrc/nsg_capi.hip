@@ -920,7 +920,7 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
                 const gr::EltSrc& S = L.srcs[i];
                 a.mode[i] = S.mode;
                 a.scalar[i] = S.scalar;
-                if (S.mode == gr::kSrcChannel || S.mode == gr::kSrcSquareChannel) a.src[i] = wts + S.constOff;
+                if (S.mode == gr::kSrcChannel || S.mode == gr::kSrcSquareChannel || S.mode == gr::kSrcSquare) a.src[i] = wts + S.constOff;
                 else if (S.mode != gr::kSrcScalar) { a.src[i] = ptr(S.v); a.stride[i] = S.v.stride; a.offset[i] = S.v.offset; }
                 a.bufLines[i] = S.v.bufLines;
                 a.line0[i] = S.v.line0;
@@ -995,6 +995,9 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
         case gr::kLaunchTokenMix:
             NSG_HIP(gr::launchGraphTokenMix(dv(L.in), wts + L.wOff, L.mixD, L.mixStages, L.act, L.mixAct2, ptr(L.out),
                                             L.out.stride, B, s));
+            break;
+        case gr::kLaunchChanReduce:
+            NSG_HIP(gr::launchGraphChanReduce(dv(L.in), L.redMode, L.scale, ptr(L.out), L.out.stride, rowsOf(L.out), s));
             break;
         case gr::kLaunchGather: {
             const int* tabs = (const int*)(wts + L.gatherTabOff); // rowTab, then colTab at the next multiple of 4 ints

@@ -116,6 +116,11 @@ void Planner::lower(const Node& N, size_t K) {
             if (It == Vals.end()) fail(N, "input '" + I + "' is not defined before its use");
             AnyRuntime = AnyRuntime || It->second.runtime;
         }
+    // an Expand of a one-channel tensor is a view that keeps the one-channel shape: only the ops that broadcast read it
+    for (const std::string& I : N.In)
+        if (!I.empty() && Vals.at(I).runtime && !Vals.at(I).expandTo.empty() && !isBinary(Op) && Op != "Max" && Op != "Min")
+            fail(N, "input '" + I + "' is " + dimsStr(Vals.at(I).dims) + " behind an Expand to " + dimsStr(Vals.at(I).expandTo) +
+                        ": the Expand is a view that only Add, Sub, Mul, Div, Max and Min read, broadcasting it themselves (DESIGN.md section 13.3)");
     if (Op == "Shape" || !AnyRuntime) return hostFold(N);
     const Val& X = get(N, 0);
     double PowOne = 0;
@@ -160,8 +165,13 @@ void Planner::lower(const Node& N, size_t K) {
         pool(N);
     } else if (Op == "Split") {
         split(N);
+    } else if (Op == "ReduceMin" || Op == "ReduceSum" || (Op == "ReduceMax" && channelAxis(N, X)) ||
+               (Op == "ReduceMean" && channelAxis(N, X) > 1)) { // (a ReduceMean over the channels of a spatial tensor: refused below, as before)
+        reduceChannels(N);
     } else if (Op == "GlobalAveragePool" || Op == "ReduceMean" || Op == "GlobalMaxPool" || Op == "ReduceMax") {
         reduceSquares(N);
+    } else if (Op == "Expand") {
+        expandView(N);
     } else if (Op == "Gather") {
         gather(N);
     } else if (X.form == kFormToken && Op != "Slice" && Op != "Identity") { // (Split on tokens is taken above)
@@ -195,6 +205,8 @@ void Planner::checkOutputs() {
         auto It = Vals.find(O);
         if (It == Vals.end()) outFail(O, "is never computed");
         if (!It->second.runtime) outFail(O, "is a constant");
+        if (!It->second.expandTo.empty())
+            outFail(O, "is " + dimsStr(It->second.dims) + " behind an Expand to " + dimsStr(It->second.expandTo) + ": the Expand is a view that only a broadcasting op reads");
         if (It->second.form == kFormLine)
             outFail(O, "is a line tensor " + dimsStr(It->second.dims) + ": it exists only between the rank / file pooling and the broadcast back onto the board (DESIGN.md section 13.3)");
         ready(O);

@@ -13,6 +13,9 @@
 // stride = C rounded up to 16 (the conv kernel's K chunk); channels C..stride-1 are written as zero by every kernel.
 // A view names a buffer plus a channel offset, so `Slice` and `Split` along the channel axis cost no launch; a view of a
 // line tensor names a first line as well, so the two halves of an 18-line block are views too.
+// A one-channel tensor ([N,1,9,9], [N,81,1], [N,1]) is an ordinary C = 1 tensor: a row of stride 16 with channel 0 live.
+// A reduction over the channels of a row (kLaunchChanReduce) writes one, and the elementwise program broadcasts one over
+// the channels of a C-channel output by reading channel 0 of its row (kSrcRowOne, kSrcBoardOne).
 #ifndef NSG_ONNX_GRAPH_H
 #define NSG_ONNX_GRAPH_H
 
@@ -76,6 +79,10 @@ enum EltMode {
     kSrcRankLine,   // broadcast over the files of a spatial output: l = (row % 81) / 9
     kSrcFileLine,   // broadcast over the ranks of a spatial output: l = (row % 81) % 9
     kSrcLine,       // a line output reading a line view of as many lines: l = row % lines (kSrcSame when the view is its whole buffer)
+    // one-channel sources broadcast over the channels of the output
+    kSrcRowOne,     // a view with C == 1 of the output's kind (spatial or token rows, or flat against flat): p[row * stride + offset]
+    kSrcBoardOne,   // a flat view with C == 1 ([N,1], [N,1,1,1]) against a spatial output: p[(row / 81) * stride + offset]
+    kSrcSquare,     // constant per square ([1,1,9,9] on a spatial tensor, [1,81,1] on tokens), 81 floats: weights[constOff + row % 81]
 };
 struct EltSrc {
     int mode = kSrcScalar;
@@ -86,10 +93,13 @@ struct EltSrc {
 
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
-    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool, kLaunchTokenMix, kLaunchGather
+    kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool, kLaunchTokenMix, kLaunchGather,
+    kLaunchChanReduce
 };
 // kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
+// kLaunchChanReduce: what is taken over the channels of a row
+enum RedMode { kRedMax = 0, kRedMin, kRedSum };
 constexpr int kMaxHeadDim = 64; // channels per attention head (a multiple of 4)
 struct CopySeg { View v; int dstOff = 0; };
 
@@ -183,6 +193,11 @@ struct Launch {
     int gatherRows = 0;
     long gatherBlock = 0;
     size_t gatherTabOff = 0;
+    // kLaunchChanReduce: the max, min or sum (redMode) over the in.C channels of every row of `in` (spatial or token rows,
+    // or flat rows; a view at any channel offset) -> out, a one-channel tensor of the same rows: channel 0 holds the
+    // result, channels 1..15 zeros.  A sum is multiplied by `scale` (the field kLaunchAttention uses) after its last add:
+    // 1 for ReduceSum, the f32 constant 1/C for a ReduceMean.
+    int redMode = kRedMax;
 };
 
 struct GraphPlan {

@@ -43,7 +43,7 @@ std::vector<size_t> constsOf(const Launch& L) {
     if (K == kLaunchAttention && L.hasBias) R = {L.biasOff};
     if (K == kLaunchGather) R = {L.gatherTabOff};
     for (const EltSrc& S : L.srcs)
-        if (S.mode == kSrcChannel || S.mode == kSrcSquareChannel) R.push_back(S.constOff);
+        if (S.mode == kSrcChannel || S.mode == kSrcSquareChannel || S.mode == kSrcSquare) R.push_back(S.constOff);
     return R;
 }
 
@@ -93,6 +93,7 @@ void dump(const GraphPlan& P) {
             std::printf(" mixD=%d mixStages=%d mixAct2=%d", L.mixD, L.mixStages, L.mixAct2);
         if (L.kind == kLaunchGather) // the source is `in`; the width is out's stride; the two tables' hash is below
             std::printf(" gatherRows=%d gatherBlock=%ld gatherWidth=%d gatherTabOff=%zu", L.gatherRows, L.gatherBlock, L.out.stride, L.gatherTabOff);
+        if (L.kind == kLaunchChanReduce) std::printf(" redMode=%d", L.redMode); // the input is `in`; the mean's factor is `scale`, above
         std::printf(" srcs=%zu", L.srcs.size());
         for (const EltSrc& S : L.srcs) {
             std::printf(" [mode=%d", S.mode);

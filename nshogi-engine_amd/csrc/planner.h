@@ -77,6 +77,7 @@ struct Val {
     int rtHead = 0;
     double rtScale = 1.0;
     int headRows = 0;           // kFormHeadRows: H; v.stride is the stride of one (board, head) row, v.C = K
+    std::vector<int64_t> expandTo; // a one-channel tensor behind an Expand: the shape the Expand names; dims stay the one-channel shape
     int lineLaunch = -1;        // kFormLine: the kLaunchLinePool that wrote it and has no other reader yet (-1: none)
     std::string chain;          // names of the nodes absorbed so far
     // the GroupNorm pattern's state ([N,G,M] behind its InstanceNormalization, until the Reshape back)
@@ -119,7 +120,7 @@ void rewritePatterns(std::vector<Node>& Nodes, std::vector<bool>& Skip, const st
 // Every device view a launch reads or writes: the lifetime pass and the renaming pass of assignBuffers go through it,
 // so a view field is named once.  F(Name, View&): the name is what the lifetimes dump prints (LifetimeTrace).
 template <class Fn> void forEachNamedView(Launch& L, Fn F) {
-    static const char* const SrcName[] = {"srcSame", "srcBoard", "", "", "", "srcRankLine", "srcFileLine", "srcLine"};
+    static const char* const SrcName[] = {"srcSame", "srcBoard", "", "", "", "srcRankLine", "srcFileLine", "srcLine", "srcRowOne", "srcBoardOne", ""};
     F("in", L.in);
     F("res", L.res);
     F("attK", L.attK);
@@ -127,7 +128,7 @@ template <class Fn> void forEachNamedView(Launch& L, Fn F) {
     F("rtBias", L.rtBias);
     F("bmmB", L.bmmB);
     for (EltSrc& S : L.srcs)
-        if (S.mode == kSrcSame || S.mode == kSrcBoard || S.mode >= kSrcRankLine) F(SrcName[S.mode], S.v);
+        if (S.mode == kSrcSame || S.mode == kSrcBoard || (S.mode >= kSrcRankLine && S.mode != kSrcSquare)) F(SrcName[S.mode], S.v);
     for (CopySeg& S : L.segs) F("seg", S.v);
     F("out", L.out);
 }
@@ -354,6 +355,8 @@ class Planner {
     // planner_pool.cc
     void pool(const Node& N);
     void reduceSquares(const Node& N);
+    int channelAxis(const Node& N, const Val& X);    // a reduction's axes are the channel axis of X: 1 spatial, 2 token, 3 flat; 0: not
+    void reduceChannels(const Node& N);              // ... as one kLaunchChanReduce
     // planner_lines.cc: rank and file pooling and the ops that read a line tensor
     void linePool(const Node& N, bool Files, bool Max);
     void lineOp(const Node& N, size_t Index);
@@ -379,6 +382,7 @@ class Planner {
                       bool Spatial);
     bool attentionOp(const Node& N); // MatMul / Mul / Div / Add / Softmax on the attention pattern's 4-D tensors
     void viewOp(const Node& N);     // Flatten / Reshape / Squeeze / Unsqueeze / Identity on a spatial or flat tensor
+    void expandView(const Node& N); // Expand of a one-channel tensor over the channels: a view
     void concat(const Node& N);
     void slice(const Node& N);
     void split(const Node& N);

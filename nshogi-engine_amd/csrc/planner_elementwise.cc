@@ -78,11 +78,21 @@ int EltBuilder::constOperand(size_t K, const Val& V) {
         S.constOff = Pl.addConst(F);
         return load(S);
     }
+    if (N.Op != "PRelu" && ((Tok && Ax == std::vector<int>{1}) || (Spatial && Ax == std::vector<int>{2, 3}))) {
+        // one value per square, [1,81,1] on tokens or [1,1,9,9] on a spatial tensor (a mask, a promotion-zone bias): 81 floats
+        if (V.count() != 81) fail("constant of shape " + dimsStr(InDims[K]) + " does not cover the squares of " + dimsStr(D));
+        std::vector<float> F(81);
+        for (size_t Sq = 0; Sq < 81; ++Sq) F[Sq] = (float)V.at(Sq);
+        EltSrc S;
+        S.mode = kSrcSquare;
+        S.constOff = Pl.addConst(F);
+        return load(S);
+    }
     if (Lines)
         fail("constant of shape " + dimsStr(InDims[K]) + " on the line tensor " + dimsStr(D) +
              ": a per-(line, channel) constant is not supported on a line tensor (per-channel and scalar constants only)");
     fail("constant of shape " + dimsStr(InDims[K]) + " broadcast to " + dimsStr(D) +
-         " (per-channel, per-(square, channel) and scalar constants only)");
+         " (per-channel, per-square, per-(square, channel) and scalar constants only)");
 }
 
 // operand K -> the register that holds it
@@ -102,13 +112,28 @@ int EltBuilder::operand(size_t K) {
                  ": a per-board value is broadcast over the 81 squares of a board only, not over its lines");
         Same = Lines && VLine && Di == D;
         const bool Back = Spatial && VLine && V.v.lines == 9 && Di[1] == C;
+        if (!Same && !Back && VLine && Di[1] == 1 && C > 1)
+            fail("the one-channel line operand " + dimsStr(Di) + " ('" + Name + "') against " + dimsStr(D) +
+                 ": a one-channel tensor is broadcast over the channels of spatial, token and flat rows only, not over the channels of lines");
         if (!Same && !Back) fail("operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
         if (Back) Map = Di[3] == 1 ? kSrcRankLine : kSrcFileLine;
     } else {
         Same = Tok ? (V.form == kFormToken && Di == D) : (Di == D || (Planner::flatC(Di) == C && !Spatial && Planner::flatC(D) == C));
         Board = !Tok && Spatial && !V.flatOfSpatial && Planner::flatC(Di) == C && Di.size() == 4;
-        if (!Same && !Board) fail("operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
+        // one channel against C > 1: channel 0 of the operand's own row, or of its board's row
+        const bool Arith = isBinary(N.Op) || N.Op == "Max" || N.Op == "Min";
+        const bool Wide = Arith && C > 1 && !V.flatOfSpatial;
+        const bool RowOne = Wide && (Tok ? V.form == kFormToken && Di == std::vector<int64_t>{kBatch, 81, 1}
+                                     : Spatial ? V.form == kFormPlain && Di == std::vector<int64_t>{kBatch, 1, 9, 9}
+                                               : V.form == kFormPlain && Planner::flatC(Di) == 1 && Planner::flatC(D) == C);
+        const bool BoardOne = Wide && !Tok && Spatial && V.form == kFormPlain && Planner::flatC(Di) == 1 && Di.size() == 4;
+        if (!Same && !Board && !RowOne && !BoardOne) fail("operand " + dimsStr(Di) + " broadcast to " + dimsStr(D) + " is not supported");
+        if (!V.expandTo.empty() && V.expandTo != D)
+            fail("'" + Name + "' is " + dimsStr(Di) + " expanded to " + dimsStr(V.expandTo) + ", the other operand makes the result " +
+                 dimsStr(D) + ": an Expand is a view only where the broadcast of its reader gives the same shape");
         if (Board) Map = kSrcBoard;
+        if (RowOne) Map = kSrcRowOne;
+        if (BoardOne) Map = kSrcBoardOne;
     }
     // an open group used only here: inline its program
     const Group* Open = V.group >= 0 ? &Pl.Groups[(size_t)V.group] : nullptr;
@@ -126,6 +151,7 @@ int EltBuilder::operand(size_t K) {
             const int RB = NG.nregs, SB = (int)NG.srcs.size();
             for (EltSrc S : Gr.srcs) {
                 if (Map != kSrcSame && (S.mode == kSrcSame || S.mode == kSrcLine)) S.mode = Map;
+                else if (Map == kSrcBoard && S.mode == kSrcRowOne) S.mode = kSrcBoardOne; // [N,1] of a flat group, now per board
                 NG.srcs.push_back(S);
             }
             for (EltInstr I : Gr.code) {

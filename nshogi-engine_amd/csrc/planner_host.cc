@@ -36,6 +36,7 @@ const std::set<std::string>& opSet() {
         "Concat", "Slice", "Identity", "Constant", "Transpose", "LayerNormalization", "Erf", "Softmax",
         "MaxPool", "AveragePool", "GlobalMaxPool", "ReduceMax", "Split", "Clip", "HardSwish", "HardSigmoid", "LeakyRelu",
         "PRelu", "Max", "Min", "Abs", "Neg", "InstanceNormalization", "Exp", "Log", "Sqrt", "Reciprocal", "Pow",
+        "ReduceMin", "ReduceSum", "Expand",
         // Shape and Cast are folded on the host only (shape chains); a Gather of a runtime tensor is planner_gather.cc's
         "Shape", "Gather", "Cast"};
     return S;

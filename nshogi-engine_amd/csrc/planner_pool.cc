@@ -110,4 +110,48 @@ void Planner::reduceSquares(const Node& N) {
     Vals[N.Out[0]] = V;
 }
 
+// ---- ReduceMax / ReduceMin / ReduceSum (and ReduceMean on token and flat rows) over the channels: one kLaunchChanReduce
+// Which kind of tensor X is when the node's axes are exactly its channel axis: 1 spatial (axis 1 of [N,C,9,9]), 2 token
+// (axis 2 of [N,81,C]), 3 flat (axis 1 of [N,C] / [N,C,1,1]); 0 otherwise.
+int Planner::channelAxis(const Node& N, const Val& X) {
+    if (!X.runtime || X.flatOfSpatial || (X.form != kFormPlain && X.form != kFormToken)) return 0;
+    if (has(N, 1) && Vals.count(N.In[1]) && Vals.at(N.In[1]).runtime) return 0;
+    const std::vector<int64_t> Axes = axes(N, X.dims.size());
+    if (Axes.size() != 1) return 0;
+    if (X.form == kFormToken) return Axes[0] == 2 ? 2 : 0;
+    if (isSpatialDims(X.dims)) return Axes[0] == 1 ? 1 : 0;
+    return flatC(X.dims) > 0 && X.dims.size() >= 2 && Axes[0] == 1 ? 3 : 0;
+}
+
+void Planner::reduceChannels(const Node& N) {
+    const std::string& Op = N.Op;
+    const Val& X = get(N, 0);
+    const std::vector<int64_t> XD = X.runtime && X.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)X.v.C * 81} : X.dims;
+    const int Kind = channelAxis(N, X);
+    if (!Kind)
+        fail(N, Op + " of " + dimsStr(XD) + ": a " + Op + " runs over the channels only, with keepdims = 1: axis 1 of [N,C,9,9] -> [N,1,9,9], "
+                "the last axis of a token tensor [N,81,C] -> [N,81,1], axis 1 of a flat [N,C] -> [N,1]");
+    const bool Keep = N.attrI("keepdims", 1) != 0;
+    if (!Keep)
+        fail(N, Op + " over axis " + std::to_string(Kind == 2 ? 2 : 1) + " of " + dimsStr(XD) + " with keepdims = 0: " +
+                    (Kind == 1 ? "[N,9,9] is ambiguous with the other 3-D shapes" : Kind == 2 ? "[N,81] is ambiguous with the other 2-D shapes"
+                                                                                               : "the result is the one-channel tensor [N,1]") +
+                    "; a reduction over the channels keeps the axis (keepdims = 1)");
+    const int C = Kind == 2 ? (int)XD[2] : (int)XD[1];
+    Launch L;
+    L.kind = kLaunchChanReduce;
+    L.name = N.Name;
+    L.redMode = Op == "ReduceMax" ? kRedMax : Op == "ReduceMin" ? kRedMin : kRedSum;
+    L.scale = Op == "ReduceMean" ? (float)(1.0 / C) : 1.f; // the mean: the sum times the f32 constant 1/C, applied after the last add
+    L.in = ready(N.In[0]).v; // a view at any channel offset: the kernel reads the ragged ends with scalar loads
+    L.out = freshView(1, Kind != 3);
+    if (L.redMode == kRedSum) P.flopsPerPosition += (double)C * (Kind == 3 ? 1 : 81);
+    std::vector<int64_t> OD = XD;
+    OD[Kind == 2 ? 2 : 1] = 1;
+    Val V = runtimeVal(N, OD, Kind == 2 ? kFormToken : kFormPlain);
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+}
+
 } // namespace nsg::graph

@@ -474,6 +474,31 @@ void Planner::viewOp(const Node& N) {
     Vals[N.Out[0]] = V;
 }
 
+// ---- Expand of a one-channel tensor to the shape its reader would broadcast it to anyway (what the exporter writes for
+// gate.expand_as(x)): a view.  The value keeps its one-channel shape and remembers the target (Val::expandTo); the Add,
+// Sub, Mul, Div, Max or Min that reads it broadcasts it (kSrcRowOne / kSrcBoardOne) and checks the target against its result.
+void Planner::expandView(const Node& N) {
+    const Val& X = get(N, 0);
+    const std::vector<int64_t> XD = X.flatOfSpatial ? std::vector<int64_t>{kBatch, (int64_t)X.v.C * 81} : X.dims;
+    const std::vector<int64_t> Sh = ints(N, 1, "the target shape");
+    std::vector<int64_t> T;
+    const bool Fits = broadcast(XD, Sh, &T);
+    const bool Plain = X.form == kFormPlain && !X.flatOfSpatial;
+    const bool View = Fits && (T == XD || (Plain && XD == std::vector<int64_t>{kBatch, 1, 9, 9} && isSpatialDims(T)) ||
+                               (Plain && flatC(XD) == 1 && XD.size() == 4 && isSpatialDims(T)) ||
+                               (X.form == kFormToken && XD == std::vector<int64_t>{kBatch, 81, 1} && isTokenDims(T)) ||
+                               (Plain && flatC(XD) == 1 && XD.size() == T.size() && flatC(T) > 0));
+    if (!View)
+        fail(N, "Expand of " + dimsStr(XD) + " to " + dimsStr(Sh) + ": only a one-channel tensor expanded over the channels is a view "
+                "([N,1,9,9] or [N,1,1,1] to [N,C,9,9], [N,81,1] to [N,81,C], [N,1] to [N,C]); nothing else is expanded");
+    const bool MoveGroup = X.group >= 0 && absorbable(N.In[0]);
+    Val V = MoveGroup ? X : ready(N.In[0]);
+    V.producer = N.Name;
+    if (T != XD) V.expandTo = T;
+    if (MoveGroup) Groups[(size_t)V.group].out = N.Out[0];
+    Vals[N.Out[0]] = V;
+}
+
 // ---- Concat along the channels: one kLaunchConcat
 void Planner::concat(const Node& N) {
     const Val& X = get(N, 0);

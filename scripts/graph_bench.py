@@ -19,6 +19,7 @@
     python scripts/graph_bench.py --group [--out profiles/graph/group_bench.json] [--repeats 3]   # the grouped-conv row
     python scripts/graph_bench.py --trace-group      # the ResNeXt net and its dense twin at B = 1, 32, 128, 512 for `rocprofv3 --kernel-trace`
     python scripts/graph_bench.py --summarize-group DIR/run_results.db [--out profiles/graph/group_bench.json]
+    python scripts/graph_bench.py --gate [--out profiles/graph/gate_bench.json] [--repeats 3]   # the scSE row
 
 Rows: the 20x256 family net forced onto the general path; the same net on the specialised fp32 and f16m6 paths; an
 SE-swish 20x256 net (squeeze-and-excitation, swish; tests/golden/make_onnx_graph_golden.py's SENet) exported at run
@@ -57,6 +58,10 @@ net, each timed `--repeats` times in turn at B = 1, 32, 128, 512.  --trace-group
 batches in one process (GROUP_FORWARDS forwards each); --summarize-group prints, per batch, the median and range of the
 grouped launch (graphConvGrouped) and of the twin's dense 3x3 256 -> 256 launch (graphConv<9>, the stem left out) and
 adds them to the --group file.
+
+--gate: the 20x256 residual net with an scSE gate in every block (tests/gate_models.py's gate_bench_net: per block one
+one-channel 1x1 conv and one elementwise launch that reads it through kSrcRowOne) beside the SE-swish net, each timed
+`--repeats` times in turn at the --batches.
 """
 import argparse
 import importlib
@@ -136,6 +141,14 @@ def mish_onnx(path, swish=False):
     import make_onnx_math_golden as mk
     torch.manual_seed(13)
     mk.export_model(mk.randomize(mk.MishBenchNet(C=86, F=256, blocks=20, act=Fn.silu if swish else Fn.mish), 21).eval(), path)
+
+
+def gate_onnx(path):
+    import torch
+    import gate_models as gm
+    import make_onnx_norm_golden as mk
+    torch.manual_seed(14)
+    mk.export_model(gm.randomize(gm.gate_bench_net(C=86, Fw=256, blocks=20), 22).eval(), path)
 
 
 def attention_onnx(path):
@@ -407,6 +420,7 @@ def main():
     ap.add_argument("--trace-norm", action="store_true", help="GroupNorm of 32, 256 and 1 groups, a 3x3 max pool and a depthwise 3x3 at B=512, C=256")
     ap.add_argument("--summarize-norm", metavar="DB", help="summarise the rocprofv3 database of a --trace-norm run")
     ap.add_argument("--mish", action="store_true", help="the 20x256 net with Mish, the same net with swish, and the forced family net")
+    ap.add_argument("--gate", action="store_true", help="the 20x256 residual net with an scSE gate per block, beside the SE-swish net")
     ap.add_argument("--repeats", type=int, default=3, help="--mish, --smolgen: times each (net, batch) is timed")
     ap.add_argument("--smolgen", action="store_true", help="the transformer with a run-time attention bias per block, and without")
     ap.add_argument("--trace-smolgen", action="store_true", help="both at B=512, 13 forwards each")
@@ -497,6 +511,25 @@ def main():
         for k, row in rows.items():
             print(k, json.dumps(row), flush=True)
         out = a.out.replace("graph_bench.json", "smolgen_bench.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump({"repeats": a.repeats, "rows": rows}, f, indent=1)
+        return
+    if a.gate:
+        paths = {k: os.path.join(tmp, k + ".onnx") for k in ("scse_20x256_general", "se_swish_20x256_general")}
+        gate_onnx(paths["scse_20x256_general"])
+        se_onnx(paths["se_swish_20x256_general"])
+        rows = {k: {} for k in paths}
+        for b in [int(b) for b in a.batches.split(",")]:
+            for rep in range(a.repeats):  # the nets in turn, so that drift of the clock falls on both
+                for k, path in paths.items():
+                    r, info = rate(nsg, path, b, iters=20 if b >= 256 else 50)
+                    rows[k].setdefault(str(b), []).append(round(r, 1))
+                    rows[k].update(path=info["path"], launches=info["launches"], conv_launches=info["conv_launches"],
+                                   flops_per_position=info["flops_per_position"])
+        for k, row in rows.items():
+            print(k, json.dumps(row), flush=True)
+        out = a.out.replace("graph_bench.json", "gate_bench.json")
         os.makedirs(os.path.dirname(out), exist_ok=True)
         with open(out, "w") as f:
             json.dump({"repeats": a.repeats, "rows": rows}, f, indent=1)
