@@ -1,6 +1,8 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
 // graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip, graph_gconv.hip, graph_tokenmix.hip,
-// graph_gather.hip, graph_chanreduce.hip).
+// graph_gather.hip, graph_chanreduce.hip).  Their one caller for a plan's launches is ../graph_exec.hip, which marshals
+// each argument record of onnx_graph.h (ConvArgs, EltProgram, ...) into the call below that runs it; nsg_capi.hip calls
+// launchGraphOutputs only.
 //
 // Every tensor is f32 in the layout of onnx_graph.h: rows (board x square, or board) of `stride` floats, channel
 // innermost, channels C..stride-1 written as zero.  A view (ptr, stride, offset) reads channels offset..offset+C-1.
@@ -46,7 +48,7 @@ hipError_t launchGraphDepthwise(const float* in, int inStride, const float* w, c
 // Grouped conv (1 < group < Cin, Cin / group a multiple of 4) of the same geometries on the f32 MFMA (graph_gconv.hip):
 // graphConvGeo's work split, but a tile of 64 outputs stages only the 16-channel input chunks its outputs' groups read
 // and each wave issues MFMAs only for the chunks of its own 16 outputs.  w: packed [tile][chunk of the tile's range]
-// [kh * kw][16][64], zeros across groups; tables: kGroupTabInts ints per tile (Launch::gTabOff); bias [tiles * 64];
+// [kh * kw][16][64], zeros across groups; tables: kGroupTabInts ints per tile (ConvArgs::gTabOff); bias [tiles * 64];
 // tiles = ceil(cout / 64); inStride and outStride multiples of 16.  An output element is one f32 chain over (chunk
 // ascending, tap row-major, the chunk's four k-steps ascending): launchGraphConv's chain restricted to the group's
 // chunks, so with Cin / group a multiple of 16 it gives the bits of a group-1 conv on the group's channel slice.  A wave
@@ -55,7 +57,7 @@ hipError_t launchGraphConvGrouped(const float* in, int inStride, const float* w,
                                   DevView res, float* out, int outStride, int cout, int kh, int kw, int dh, int dw,
                                   int boards, int act, hipStream_t stream);
 
-// Fused elementwise chain (the program of onnx_graph.h's EltInstr / EltSrc) over `rows` rows.
+// Fused elementwise chain (onnx_graph.h's EltProgram, marshaled for the device) over `rows` rows.
 struct EltArgs {
     const float* src[kMaxEltSrcs];
     int stride[kMaxEltSrcs];

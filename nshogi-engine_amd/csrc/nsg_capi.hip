@@ -10,7 +10,8 @@
 #include "kernels/kernels.h"
 #include "onnx_reader.h"
 #include "onnx_graph.h"
-#include "kernels/graph_kernels.h"
+#include "graph_exec.h"
+#include "kernels/graph_kernels.h" // launchGraphOutputs: the output scatter (the plan's launches go through graph_exec.h)
 
 #include <hip/hip_runtime.h>
 
@@ -337,6 +338,7 @@ struct nsg_evaluator {
     std::shared_ptr<GraphWeights> G;
     DevBuf gPlanes;               // [batchMax * 81][planeStride] f32 input planes
     std::vector<DevBuf> gAct;     // the plan's activation buffers, sized for batchMax
+    std::vector<float*> gActPtr;  // ... and their device pointers, as graph_exec.h's GraphBufs takes them
     int graphMode = 0;            // nsg_set_graph_mode
     int loadedNodes = 0;          // ONNX nodes of a family model on the specialised path (0: an NSGW blob)
     int lastTrunkPrec = -1; // precision the most recent forward ran its trunk in
@@ -861,14 +863,12 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
     namespace gr = nsg::graph;
     hipStream_t s = ev->stream;
     const gr::GraphPlan& P = *ev->G->plan;
-    const float* wts = (const float*)ev->G->w.p;
-    auto ptr = [&](const gr::View& v) -> float* { return v.buf < 0 ? (float*)ev->gPlanes.p : (float*)ev->gAct[(size_t)v.buf].p; };
-    auto dv = [&](const gr::View& v) {
+    const gr::GraphBufs bufs{(float*)ev->gPlanes.p, ev->gActPtr.data(), (const float*)ev->G->w.p};
+    auto dv = [&](const gr::View& v) { // (the three output views)
         gr::DevView d;
-        d.p = ptr(v); d.stride = v.stride; d.offset = v.offset; d.C = v.C;
+        d.p = v.buf < 0 ? bufs.planes : bufs.act[(size_t)v.buf]; d.stride = v.stride; d.offset = v.offset; d.C = v.C;
         return d;
     };
-    auto rowsOf = [&](const gr::View& v) -> long { return v.spatial ? (long)B * 81 : v.lines ? (long)B * v.lines : (long)B; };
     const bool prof = ev->profile;
     if (prof && ev->evUsed + 4 > (int)ev->ev.size()) {
         int rc = drainProfile(ev);
@@ -888,126 +888,11 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
                                       nsg::kFp32, s));
     if (prof && P.convLaunches == 0) { NSG_HIP(hipEventRecord(e[1], s)); NSG_HIP(hipEventRecord(e[2], s)); }
     int convs = 0;
-    for (const gr::Launch& L : P.launches) {
-        switch (L.kind) {
-        case gr::kLaunchConv: {
-            if (prof && convs == 0) NSG_HIP(hipEventRecord(e[1], s));
-            gr::DevView res;
-            if (L.res.buf != -2) res = dv(L.res);
-            // a dense layer runs over groups of 81 rows: boards, or the (board, head) rows of a head-row tensor
-            const long denseRows = (long)B * L.rowsPerBoard;
-            const int groups = L.dense ? (int)((denseRows + 80) / 81) : B;
-            if (L.depthwise)
-                NSG_HIP(gr::launchGraphDepthwise(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out),
-                                                 L.out.stride, L.out.C, L.kh, L.kw, L.dh, L.dw, B, L.act, s));
-            else if (L.groups > 1)
-                NSG_HIP(gr::launchGraphConvGrouped(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff,
-                                                   (const int*)(wts + L.gTabOff), res, ptr(L.out), L.out.stride, L.out.C,
-                                                   L.kh, L.kw, L.dh, L.dw, B, L.act, s));
-            else if (L.kh == L.kw && (L.kh == 1 || L.kh == 3) && L.dh == 1 && L.dw == 1)
-                NSG_HIP(gr::launchGraphConv(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out), L.out.stride,
-                                            L.out.C, L.cinPad, L.coutTiles, L.taps, groups, L.dense ? denseRows : rowsOf(L.out),
-                                            L.act, s));
-            else
-                NSG_HIP(gr::launchGraphConvGeo(ptr(L.in), L.in.stride, wts + L.wOff, wts + L.biasOff, res, ptr(L.out),
-                                               L.out.stride, L.out.C, L.cinPad, L.coutTiles, L.kh, L.kw, L.dh, L.dw, B, L.act, s));
-            if (prof && ++convs == P.convLaunches) NSG_HIP(hipEventRecord(e[2], s));
-            break;
-        }
-        case gr::kLaunchElt: {
-            gr::EltArgs a{};
-            for (size_t i = 0; i < L.srcs.size(); ++i) {
-                const gr::EltSrc& S = L.srcs[i];
-                a.mode[i] = S.mode;
-                a.scalar[i] = S.scalar;
-                if (S.mode == gr::kSrcChannel || S.mode == gr::kSrcSquareChannel || S.mode == gr::kSrcSquare) a.src[i] = wts + S.constOff;
-                else if (S.mode != gr::kSrcScalar) { a.src[i] = ptr(S.v); a.stride[i] = S.v.stride; a.offset[i] = S.v.offset; }
-                a.bufLines[i] = S.v.bufLines;
-                a.line0[i] = S.v.line0;
-            }
-            a.outLines = L.out.lines;
-            for (size_t i = 0; i < L.code.size(); ++i)
-                a.code[i] = (uint32_t)L.code[i].op | (uint32_t)L.code[i].dst << 8 | (uint32_t)L.code[i].a << 16 | (uint32_t)L.code[i].b << 24;
-            a.ncode = (int)L.code.size();
-            a.outReg = L.eltOut;
-            a.out = ptr(L.out);
-            a.outStride = L.out.stride;
-            a.C = L.out.C;
-            a.rows = rowsOf(L.out);
-            NSG_HIP(gr::launchGraphElt(a, s));
-            break;
-        }
-        case gr::kLaunchMean:
-            NSG_HIP(gr::launchGraphMean(dv(L.in), ptr(L.out), L.out.stride, B, s));
-            break;
-        case gr::kLaunchMax:
-            NSG_HIP(gr::launchGraphMax(dv(L.in), ptr(L.out), L.out.stride, B, s));
-            break;
-        case gr::kLaunchPool:
-            NSG_HIP(gr::launchGraphPool(dv(L.in), ptr(L.out), L.out.stride, L.kh, L.kw, L.dh, L.dw, L.poolMode, B, s));
-            break;
-        case gr::kLaunchLinePool:
-            NSG_HIP(gr::launchGraphLinePool(dv(L.in), ptr(L.out), L.out.stride, L.out.bufLines, L.out.line0, L.lineFiles,
-                                            L.poolMode, B, s));
-            break;
-        case gr::kLaunchConcat: {
-            gr::ConcatArgs a{};
-            for (size_t i = 0; i < L.segs.size(); ++i) {
-                a.src[i] = ptr(L.segs[i].v); a.stride[i] = L.segs[i].v.stride; a.offset[i] = L.segs[i].v.offset;
-                a.count[i] = L.segs[i].v.C; a.dstOff[i] = L.segs[i].dstOff;
-            }
-            a.nseg = (int)L.segs.size();
-            a.out = ptr(L.out);
-            a.outStride = L.out.stride;
-            a.rows = rowsOf(L.out);
-            NSG_HIP(gr::launchGraphConcat(a, s));
-            break;
-        }
-        case gr::kLaunchLayerNorm:
-            NSG_HIP(gr::launchGraphLayerNorm(dv(L.in), wts + L.wOff, wts + L.biasOff, L.eps, ptr(L.out), L.out.stride, rowsOf(L.out), s));
-            break;
-        case gr::kLaunchGroupNorm:
-            NSG_HIP(gr::launchGraphGroupNorm(dv(L.in), L.groups, wts + L.wOff, wts + L.biasOff, L.eps, L.act, ptr(L.out),
-                                             L.out.stride, B, s));
-            break;
-        case gr::kLaunchRmsNorm:
-            NSG_HIP(gr::launchGraphRmsNorm(dv(L.in), wts + L.wOff, L.eps, ptr(L.out), L.out.stride, rowsOf(L.out), s));
-            break;
-        case gr::kLaunchAttention: {
-            gr::RtBias rt;
-            if (L.hasRtBias) {
-                rt.p = ptr(L.rtBias) + L.rtBias.offset;
-                rt.boardStride = L.rtBias.stride;
-                rt.headStride = L.rtHeadStride;
-                rt.scale = L.rtScale;
-            }
-            NSG_HIP(gr::launchGraphAttention(dv(L.in), dv(L.attK), dv(L.attV), L.hasBias ? wts + L.biasOff : nullptr, L.scale,
-                                             rt, ptr(L.out), L.out.stride, L.heads, L.headDim, B, s));
-            break;
-        }
-        case gr::kLaunchFlatten:
-            NSG_HIP(gr::launchGraphFlatten(dv(L.in), ptr(L.out), L.out.stride, B, s));
-            break;
-        case gr::kLaunchBmm:
-            if (L.bmmNN) NSG_HIP(gr::launchGraphBmmNN(dv(L.in), dv(L.bmmB), L.scale, L.act, ptr(L.out), L.out.stride, B, s));
-            else NSG_HIP(gr::launchGraphBmmNT(dv(L.in), dv(L.bmmB), L.scale, L.act, ptr(L.out), L.out.stride, B, s));
-            break;
-        case gr::kLaunchTokenMix:
-            NSG_HIP(gr::launchGraphTokenMix(dv(L.in), wts + L.wOff, L.mixD, L.mixStages, L.act, L.mixAct2, ptr(L.out),
-                                            L.out.stride, B, s));
-            break;
-        case gr::kLaunchChanReduce:
-            NSG_HIP(gr::launchGraphChanReduce(dv(L.in), L.redMode, L.scale, ptr(L.out), L.out.stride, rowsOf(L.out), s));
-            break;
-        case gr::kLaunchGather: {
-            const int* tabs = (const int*)(wts + L.gatherTabOff); // rowTab, then colTab at the next multiple of 4 ints
-            NSG_HIP(gr::launchGraphGather(ptr(L.in), L.gatherBlock, tabs, tabs + (L.gatherRows + 3) / 4 * 4, ptr(L.out),
-                                          L.out.stride, L.out.C, L.gatherRows, B, s));
-            break;
-        }
-        default:
-            return fail(NSG_E_INVALID, "internal error: unknown launch kind %d in the graph plan", L.kind);
-        }
+    for (const gr::Launch& L : P.launches) { // each launch: graph_exec.hip
+        const bool conv = L.is<gr::ConvArgs>();
+        if (prof && conv && convs == 0) NSG_HIP(hipEventRecord(e[1], s));
+        NSG_HIP(gr::runLaunch(L, bufs, B, s));
+        if (prof && conv && ++convs == P.convLaunches) NSG_HIP(hipEventRecord(e[2], s));
     }
     NSG_HIP(gr::launchGraphOutputs(dv(P.policy), P.policy.spatial, dv(P.value), dv(P.draw), (float*)ev->policy.p,
                                    (float*)ev->value.p, (float*)ev->draw.p, B, s));
@@ -1270,6 +1155,7 @@ int finishLoad(nsg_evaluator* ev, std::shared_ptr<NetWeights> W) {
     const int es = nsg::elemSize(prec);
     ev->G.reset();
     ev->gAct.clear();
+    ev->gActPtr.clear();
     ev->gPlanes.release();
     ev->loadedNodes = 0;
     ev->W = std::move(W);
@@ -1390,9 +1276,12 @@ int finishGraphLoad(nsg_evaluator* ev, std::shared_ptr<GraphWeights> G) {
     ev->coopEnabled = 0;
     if ((rc = ev->gPlanes.alloc((size_t)ev->batchMax * 81 * P.planeStride * sizeof(float), true))) return rc;
     ev->gAct.clear();
+    ev->gActPtr.clear();
     ev->gAct.resize(P.bufSpatialStride.size());
-    for (size_t i = 0; i < ev->gAct.size(); ++i)
+    for (size_t i = 0; i < ev->gAct.size(); ++i) {
         if ((rc = ev->gAct[i].alloc(nsg::graph::bufferFloats(P, i, ev->batchMax) * sizeof(float), true))) return rc;
+        ev->gActPtr.push_back((float*)ev->gAct[i].p);
+    }
     NSG_HIP(hipDeviceSynchronize());
     ev->loaded = true;
     return NSG_OK;

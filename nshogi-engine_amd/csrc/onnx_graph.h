@@ -1,6 +1,8 @@
 // onnx_graph.h -- the general graph path's host half: reads an ONNX model built from the closed op set of
 // DESIGN.md section 13, folds shape chains and BatchNorm, fuses epilogues and elementwise chains, assigns
-// activation buffers, and returns an immutable GraphPlan of launch records.  Host-only C++: no device code.
+// activation buffers, and returns an immutable GraphPlan of launches: each a name, an output view and the argument
+// record of its kind (ConvArgs, EltProgram, ... below), which also names the device views the launch reads.
+// graph_exec.hip runs a launch on the device, one function per record.  Host-only C++: no device code.
 //
 // Layout of every runtime tensor (the library's board-major, channel-innermost layout):
 //   spatial [N,C,9,9]           -> [row = board * 81 + square][stride] floats
@@ -22,6 +24,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <variant>
 #include <vector>
 
 namespace nsg {
@@ -34,7 +37,7 @@ constexpr int kMaxEltSrcs = 8;  // inputs of one fused elementwise launch
 constexpr int kMaxEltCode = 32; // instructions of one fused elementwise launch
 constexpr int kMaxEltRegs = 16;
 constexpr int kMaxCopySegs = 8; // sources of one channel concat
-constexpr int kGroupTabInts = 12; // ints per 64-output tile in a grouped conv's table (Launch::gTabOff)
+constexpr int kGroupTabInts = 12; // ints per 64-output tile in a grouped conv's table (ConvArgs::gTabOff)
 constexpr int kMaxMixHidden = 336; // hidden units of a token-mixing MLP: 21 fragments of 16 (an expansion of 4 x 81 = 324 fits)
 
 // kActGelu: exact (erf); kActRelu6 = min(max(x, 0), 6); kActHardSigmoid = min(max(x / 6 + 0.5, 0), 1); kActHardSwish =
@@ -58,6 +61,12 @@ struct View {
     // per board; row (board, l) of the view is row board * bufLines + line0 + l of the buffer
     int lines = 0, bufLines = 0, line0 = 0;
 };
+constexpr int kNoRes = -2; // View::buf of a conv's `res` that has no residual
+inline View noResidual() {
+    View V;
+    V.buf = kNoRes;
+    return V;
+}
 
 // Elementwise program: registers r0..r15; opcodes below.  LOAD reads source `a` into register `dst`.
 // kEltLeaky: dst = a > 0 ? a : a * b (LeakyRelu: b holds alpha; PRelu: b holds the channel's slope); kEltNeg, kEltAbs: of a.
@@ -91,28 +100,29 @@ struct EltSrc {
     float scalar = 0.f;
 };
 
+// The numeric values are printed by plan_dump (kind=%d): they do not change.
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
     kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool, kLaunchTokenMix, kLaunchGather,
     kLaunchChanReduce
 };
-// kLaunchPool: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
+// PoolArgs: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
-// kLaunchChanReduce: what is taken over the channels of a row
+// ChanReduceArgs: what is taken over the channels of a row
 enum RedMode { kRedMax = 0, kRedMin, kRedSum };
 constexpr int kMaxHeadDim = 64; // channels per attention head (a multiple of 4)
 struct CopySeg { View v; int dstOff = 0; };
 
-struct Launch {
-    int kind = kLaunchConv;
-    std::string name; // the ONNX node(s) it runs
-    View out;
-    // kLaunchConv: an implicit-GEMM conv (taps = kh x kw, row-major over (ky, kx)), a dense layer (taps 1, rows =
-    // boards) or a depthwise conv.  A tap reads the square (ky - (kh-1)/2) * dh rows and (kx - (kw-1)/2) * dw columns
-    // away; the halo dh * (kh-1)/2 by dw * (kw-1)/2 is at most kMaxConvHalo each way.  1x1 and 3x3 at dilation 1 run
-    // on graphConv<1> / graphConv<9>, every other dense geometry on graphConvGeo, depthwise on graphDepthwise, a grouped
-    // conv (groups > 1, below) of any geometry on graphConvGrouped.
-    View in, res;    // res.buf == -2: no residual
+// ---- The argument records: one per launch kind (or family of kinds), holding that kind's fields only.  A Launch is a
+// name, the output view and one record; its kind is read off the record (kind()), so a kind and another kind's fields
+// cannot meet.  views(F) calls F(name, View&) for every device view the record reads: the one place a view field is
+// named for the lifetime pass and the buffer renaming (forEachNamedView, planner.h).  `out` is the Launch's own.
+
+// kLaunchConv: an implicit-GEMM conv (taps = kh x kw, row-major over (ky, kx)), a dense layer (taps 1, rows =
+// boards) or a depthwise conv.  A tap reads the square (ky - (kh-1)/2) * dh rows and (kx - (kw-1)/2) * dw columns
+// away; the halo dh * (kh-1)/2 by dw * (kw-1)/2 is at most kMaxConvHalo each way.  Which kernel runs it: kernel().
+struct ConvArgs {
+    View in, res = noResidual();
     bool dense = false;
     bool depthwise = false; // group = Cin = Cout: per-channel taps, no sum over channels
     int taps = 9;
@@ -121,40 +131,131 @@ struct Launch {
     int coutTiles = 0;  // depthwise: unused (0)
     size_t wOff = 0;    // packed weights [coutTiles][cinPad / 16][taps][16][64]; depthwise: [cinPad / 16][taps][16]
     size_t biasOff = 0; // [coutTiles * 64]; depthwise: [cinPad]
-    // A grouped conv (1 < group < Cin, Cin / group a multiple of 4) is a kLaunchConv with `groups` > 1 (the field is
-    // shared with kLaunchGroupNorm, below).  Its packed weights are [tile][chunk of the tile's range][tap][16][64]: a
-    // tile of 64 outputs holds only the 16-channel input chunks that the groups of its outputs read, with exact zeros
-    // where input and output channel lie in different groups.  gTabOff: kGroupTabInts ints per tile, stored bit for
-    // bit in the float blob: first chunk, chunk count, the tile's weight offset in floats from wOff, 0, then
-    // (first chunk, chunk count) of each of the four waves' 16 outputs (a sub-range of the tile's; count 0: no output).
+    // A grouped conv (1 < group < Cin, Cin / group a multiple of 4) has `groups` > 1.  Its packed weights are [tile]
+    // [chunk of the tile's range][tap][16][64]: a tile of 64 outputs holds only the 16-channel input chunks that the
+    // groups of its outputs read, with exact zeros where input and output channel lie in different groups.  gTabOff:
+    // kGroupTabInts ints per tile, stored bit for bit in the float blob: first chunk, chunk count, the tile's weight
+    // offset in floats from wOff, 0, then (first chunk, chunk count) of each of the four waves' 16 outputs (a sub-range
+    // of the tile's; count 0: no output).
+    int groups = 1;
     size_t gTabOff = 0;
     int act = kActNone;
-    // kLaunchElt
+    // dense: the rows of a board.  1: flat [N,K]; H: head rows [N,H,K], rows of (board, head) at stride in.stride, H of
+    // them contiguous per board (the virtual buffer is flat with stride H * in.stride); L: a line tensor's (board, line)
+    // rows, a 1x1 conv over them.
+    int rowsPerBoard = 1;
+
+    // The kernel of graph_kernels.h that runs the conv: depthwise on graphDepthwise, a grouped conv of any geometry on
+    // graphConvGrouped, 1x1 and 3x3 at dilation 1 (and every dense layer) on graphConv<1> / graphConv<9>, every other
+    // dense geometry on graphConvGeo.
+    enum Kernel { kDepthwise, kGrouped, kTile, kGeo };
+    Kernel kernel() const {
+        if (depthwise) return kDepthwise;
+        if (groups > 1) return kGrouped;
+        return kh == kw && (kh == 1 || kh == 3) && dh == 1 && dw == 1 ? kTile : kGeo;
+    }
+    static constexpr int kind() { return kLaunchConv; }
+    template <class Fn> void views(Fn F) { F("in", in); F("res", res); }
+};
+
+// kLaunchElt: the fused elementwise program over the rows of `out` (the device-side marshaled form is EltArgs,
+// graph_kernels.h)
+struct EltProgram {
     std::vector<EltSrc> srcs;
     std::vector<EltInstr> code;
     int eltOut = 0;  // the register stored
-    // kLaunchMean / kLaunchMax / kLaunchFlatten: `in`; kLaunchConcat: segments
+    static constexpr int kind() { return kLaunchElt; }
+    template <class Fn> void views(Fn F) { // a source that reads a device view is named by its mode
+        static const char* const Name[] = {"srcSame", "srcBoard", "", "", "", "srcRankLine", "srcFileLine", "srcLine", "srcRowOne", "srcBoardOne", ""};
+        for (EltSrc& S : srcs)
+            if (S.mode == kSrcSame || S.mode == kSrcBoard || (S.mode >= kSrcRankLine && S.mode != kSrcSquare)) F(Name[S.mode], S.v);
+    }
+};
+
+// kLaunchMean / kLaunchMax: the mean or the max (`max`) over the 81 squares of `in` -> a flat out
+struct SquareReduceArgs {
+    View in;
+    bool max = false;
+    int kind() const { return max ? kLaunchMax : kLaunchMean; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchConcat: the segments side by side along the channels (one segment: a plain copy)
+struct ConcatSegs {
     std::vector<CopySeg> segs;
-    // kLaunchPool: `in` (a spatial view at any channel offset) -> out, kh x kw taps at dilations dh, dw under the conv's
-    // halo rule, stride 1: the board stays 9x9
+    static constexpr int kind() { return kLaunchConcat; }
+    template <class Fn> void views(Fn F) {
+        for (CopySeg& S : segs) F("seg", S.v);
+    }
+};
+
+// kLaunchFlatten: a spatial `in` -> the flat [N,C*81] in ONNX order
+struct FlattenArgs {
+    View in;
+    static constexpr int kind() { return kLaunchFlatten; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchPool: `in` (a spatial view at any channel offset) -> out, kh x kw taps at dilations dh, dw under the conv's
+// halo rule, stride 1: the board stays 9x9
+struct PoolArgs {
+    View in;
+    int kh = 3, kw = 3, dh = 1, dw = 1;
     int poolMode = kPoolMax;
-    // kLaunchLinePool: `in` (a spatial view at any channel offset) -> out, a 9-line view: the max (kPoolMax) or the mean
-    // (kPoolAvgInclude) of each rank over its files (lineFiles false, [N,C,9,1]) or of each file over its ranks (true,
-    // [N,C,1,9]).  out.line0 / out.bufLines place the nine lines inside an 18-line block.
+    static constexpr int kind() { return kLaunchPool; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchLinePool: `in` (a spatial view at any channel offset) -> out, a 9-line view: the max (kPoolMax) or the mean
+// (kPoolAvgInclude) of each rank over its files (lineFiles false, [N,C,9,1]) or of each file over its ranks (true,
+// [N,C,1,9]).  out.line0 / out.bufLines place the nine lines inside an 18-line block.
+struct LinePoolArgs {
+    View in;
     bool lineFiles = false;
-    // kLaunchLayerNorm: over the channels of each row of `in` (token rows or boards); gamma at wOff, beta at biasOff
+    int poolMode = kPoolMax;
+    static constexpr int kind() { return kLaunchLinePool; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchLayerNorm: over the channels of each row of `in` (token rows or boards); gamma at wOff, beta at biasOff
+struct LayerNormArgs {
+    View in;
+    size_t wOff = 0, biasOff = 0;
     float eps = 0.f;
-    // kLaunchGroupNorm: `in` (a spatial view at any channel offset) normalised per (board, group of C / groups consecutive
-    // channels), then gamma at wOff, beta at biasOff (both [C], the pattern's constants folded in double) and `act`.
-    // kLaunchRmsNorm: x / sqrt(mean(x^2) + eps) * gamma over the channels of each row of `in`; gamma at wOff
+    static constexpr int kind() { return kLaunchLayerNorm; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchGroupNorm: `in` (a spatial view at any channel offset) normalised per (board, group of C / groups consecutive
+// channels), then gamma at wOff, beta at biasOff (both [C], the pattern's constants folded in double) and `act`
+struct GroupNormArgs {
+    View in;
+    size_t wOff = 0, biasOff = 0;
+    float eps = 0.f;
     int groups = 1;
-    // kLaunchAttention: softmax(scale * q k^T + bias) v per (board, head) over the 81 squares.  q = `in`, k, v: token
-    // views of heads * headDim channels; bias (hasBias): [heads][81][81] at biasOff; out: token rows, head h at
-    // channels h * headDim
-    View attK, attV;
+    int act = kActNone;
+    static constexpr int kind() { return kLaunchGroupNorm; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchRmsNorm: x / sqrt(mean(x^2) + eps) * gamma over the channels of each row of `in`; gamma at wOff
+struct RmsNormArgs {
+    View in;
+    size_t wOff = 0;
+    float eps = 0.f;
+    static constexpr int kind() { return kLaunchRmsNorm; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchAttention: softmax(scale * q k^T + bias) v per (board, head) over the 81 squares.  q = `in`, k, v: token
+// views of heads * headDim channels; bias (hasBias): [heads][81][81] at biasOff; out: token rows, head h at
+// channels h * headDim
+struct AttentionArgs {
+    View in, attK, attV;
     int heads = 0, headDim = 0;
     float scale = 1.f;
     bool hasBias = false;
+    size_t biasOff = 0;
     // ... plus rtScale times a bias computed at run time (hasRtBias): rtBias is a flat view whose stride is the floats
     // from one board to the next; head h, query q, key j at offset + h * rtHeadStride + q * 81 + j of the board's row.
     // rtHeadStride 0: one bias for all heads ([N,1,81,81]); 6561: a flat [N,H*6561]; 6576: head rows [N,H,6561].
@@ -163,41 +264,84 @@ struct Launch {
     int rtHeadStride = 0;
     float rtScale = 1.f;
     bool hasRtBias = false;
-    // kLaunchConv, dense: the rows of a board.  1: flat [N,K]; H: head rows [N,H,K], rows of (board, head) at stride
-    // in.stride, H of them contiguous per board (the virtual buffer is flat with stride H * in.stride); L: a line
-    // tensor's (board, line) rows, a 1x1 conv over them.
-    int rowsPerBoard = 1;
-    // kLaunchBmm: the product of two run-time token tensors per board, out = act(scale * sum), the sum first, then the
-    // scalar, then `act` (a parameter-free Act).  A = `in`, B = `bmmB`, both token views at offsets that are multiples of 4.
-    // NT (bmmNN false): A [N,81,bmmK], B [N,81,bmmK] (the rows of the graph's [N,K,81] operand), out[n,i,j] = sum_k
-    // A[n,i,k] B[n,j,k], a token tensor of 81 channels.  NN: A [N,81,81], B [N,81,M], out[n,i,c] = sum_j A[n,i,j] B[n,j,c],
-    // bmmK = 81.
-    View bmmB;
+    static constexpr int kind() { return kLaunchAttention; }
+    template <class Fn> void views(Fn F) {
+        F("in", in); F("attK", attK); F("attV", attV);
+        if (hasRtBias) F("rtBias", rtBias);
+    }
+};
+
+// kLaunchBmm: the product of two run-time token tensors per board, out = act(scale * sum), the sum first, then the
+// scalar, then `act` (a parameter-free Act).  A = `in`, B = `bmmB`, both token views at offsets that are multiples of 4.
+// NT (bmmNN false): A [N,81,bmmK], B [N,81,bmmK] (the rows of the graph's [N,K,81] operand), out[n,i,j] = sum_k
+// A[n,i,k] B[n,j,k], a token tensor of 81 channels.  NN: A [N,81,81], B [N,81,M], out[n,i,c] = sum_j A[n,i,j] B[n,j,c],
+// bmmK = 81.
+struct BmmArgs {
+    View in, bmmB;
     bool bmmNN = false;
     int bmmK = 0;
-    // kLaunchTokenMix: a Linear over the 81 squares of every channel of `in` (a spatial view of C channels at an offset
-    // that is a multiple of 4), one stage or two: out[n,j,c] = act2(sum_d W2[d][j] h[n,d,c] + b2[j]) with h[n,d,c] =
-    // act(sum_s W1[s][d] in[n,s,c] + b1[d]), mixD hidden units (mixStages 2); or out = h with mixD = 81 (mixStages 1).
-    // One constant record at wOff, with Dp = mixD rounded up to 16: W1 transposed [Dp][84], b1 [Dp], then for two
-    // stages W2 transposed [96][Dp] and b2 [96], every pad zero.  act, mixAct2: parameter-free Acts.
+    float scale = 1.f;
+    int act = kActNone;
+    static constexpr int kind() { return kLaunchBmm; }
+    template <class Fn> void views(Fn F) { F("in", in); F("bmmB", bmmB); }
+};
+
+// kLaunchTokenMix: a Linear over the 81 squares of every channel of `in` (a spatial view of C channels at an offset
+// that is a multiple of 4), one stage or two: out[n,j,c] = act2(sum_d W2[d][j] h[n,d,c] + b2[j]) with h[n,d,c] =
+// act(sum_s W1[s][d] in[n,s,c] + b1[d]), mixD hidden units (mixStages 2); or out = h with mixD = 81 (mixStages 1).
+// One constant record at wOff, with Dp = mixD rounded up to 16: W1 transposed [Dp][84], b1 [Dp], then for two
+// stages W2 transposed [96][Dp] and b2 [96], every pad zero.  act, mixAct2: parameter-free Acts.
+struct TokenMixArgs {
+    View in;
+    size_t wOff = 0;
     int mixD = 0;
     int mixStages = 0;
+    int act = kActNone;
     int mixAct2 = kActNone;
-    // kLaunchGather: a Gather with constant indices, or a board flip.  Per board the output has gatherRows rows (81: spatial
-    // or token rows; 1: a flat row) of out.stride floats, and the source is a block of gatherBlock floats (81 * in.stride for
-    // spatial or token rows, in.stride for a flat row) in `in`'s buffer.  Output element (r, c), c < out.C, is
-    // src[board * gatherBlock + rowTab[r] + colTab[c]] (in.offset is inside colTab); elements c >= out.C are zero.  The
-    // two int tables lie at gatherTabOff, stored bit for bit in the float blob as a grouped conv's table is: rowTab
-    // [gatherRows], then colTab[out.stride] with pad entries 0, each 16-byte aligned.  The planner checks every entry:
-    // max(rowTab) + max(colTab) < gatherBlock, none negative.  The device checks nothing.
+    static constexpr int kind() { return kLaunchTokenMix; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchGather: a Gather with constant indices, or a board flip.  Per board the output has gatherRows rows (81: spatial
+// or token rows; 1: a flat row) of out.stride floats, and the source is a block of gatherBlock floats (81 * in.stride for
+// spatial or token rows, in.stride for a flat row) in `in`'s buffer.  Output element (r, c), c < out.C, is
+// src[board * gatherBlock + rowTab[r] + colTab[c]] (in.offset is inside colTab); elements c >= out.C are zero.  The
+// two int tables lie at gatherTabOff, stored bit for bit in the float blob as a grouped conv's table is: rowTab
+// [gatherRows], then colTab[out.stride] with pad entries 0, each 16-byte aligned.  The planner checks every entry:
+// max(rowTab) + max(colTab) < gatherBlock, none negative.  The device checks nothing.
+struct GatherArgs {
+    View in;
     int gatherRows = 0;
     long gatherBlock = 0;
     size_t gatherTabOff = 0;
-    // kLaunchChanReduce: the max, min or sum (redMode) over the in.C channels of every row of `in` (spatial or token rows,
-    // or flat rows; a view at any channel offset) -> out, a one-channel tensor of the same rows: channel 0 holds the
-    // result, channels 1..15 zeros.  A sum is multiplied by `scale` (the field kLaunchAttention uses) after its last add:
-    // 1 for ReduceSum, the f32 constant 1/C for a ReduceMean.
+    static constexpr int kind() { return kLaunchGather; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+// kLaunchChanReduce: the max, min or sum (redMode) over the in.C channels of every row of `in` (spatial or token rows,
+// or flat rows; a view at any channel offset) -> out, a one-channel tensor of the same rows: channel 0 holds the
+// result, channels 1..15 zeros.  A sum is multiplied by `scale` after its last add: 1 for ReduceSum, the f32 constant
+// 1/C for a ReduceMean.
+struct ChanReduceArgs {
+    View in;
     int redMode = kRedMax;
+    float scale = 1.f;
+    static constexpr int kind() { return kLaunchChanReduce; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
+using LaunchArgs = std::variant<ConvArgs, EltProgram, SquareReduceArgs, ConcatSegs, FlattenArgs, LayerNormArgs, AttentionArgs,
+                                PoolArgs, GroupNormArgs, RmsNormArgs, BmmArgs, LinePoolArgs, TokenMixArgs, GatherArgs,
+                                ChanReduceArgs>;
+
+struct Launch {
+    std::string name; // the ONNX node(s) it runs
+    View out;
+    LaunchArgs args;
+    int kind() const { // a LaunchKind
+        return std::visit([](const auto& A) -> int { return A.kind(); }, args);
+    }
+    template <class T> bool is() const { return std::holds_alternative<T>(args); }
 };
 
 struct GraphPlan {

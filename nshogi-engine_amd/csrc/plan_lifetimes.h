@@ -10,7 +10,7 @@ namespace nsg {
 namespace graph {
 
 struct ViewTrace {
-    std::string field; // the view's name in forEachNamedView (planner.h); an elementwise source is named by its mode
+    std::string field; // the view's name in its record's views() (onnx_graph.h); an elementwise source is named by its mode
     int virt = -1;     // its virtual buffer before the renaming (-1: the plane buffer, -2: no residual)
     View v;            // the view as the launch sees it, renamed
 };

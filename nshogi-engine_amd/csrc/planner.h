@@ -1,5 +1,7 @@
 // planner.h -- what the planner's translation units share (onnx_graph.cc and planner_*.cc).
-// Internal: not installed, and not included by nsg_capi.hip, which sees onnx_graph.h only.
+// Internal: not installed, and not included by nsg_capi.hip or graph_exec.hip, which see onnx_graph.h only.
+// A planner method builds the argument record of its launch's kind (onnx_graph.h) and hands the Launch to emit(); the
+// record names its own device views, so nothing here lists view fields.
 #ifndef NSG_PLANNER_H
 #define NSG_PLANNER_H
 
@@ -17,7 +19,6 @@ namespace nsg::graph {
 using namespace nsg::onnx::wire;
 
 constexpr int64_t kBatch = INT64_MIN / 2; // the symbolic batch dimension inside folded shape values
-constexpr int kNoRes = -2;
 constexpr int kPending = -3; // the view of an open elementwise group: its buffer is assigned when the group is emitted
 
 inline int roundUp(int a, int b) { return (a + b - 1) / b * b; }
@@ -117,19 +118,11 @@ std::vector<int> variesAlong(const std::vector<int64_t>& D, size_t R);
 void rewritePatterns(std::vector<Node>& Nodes, std::vector<bool>& Skip, const std::map<std::string, Tensor>& Inits,
                      const std::set<std::string>& Outputs);
 
-// Every device view a launch reads or writes: the lifetime pass and the renaming pass of assignBuffers go through it,
-// so a view field is named once.  F(Name, View&): the name is what the lifetimes dump prints (LifetimeTrace).
+// Every device view a launch reads or writes: the lifetime pass and the renaming pass of assignBuffers go through it.
+// The views a launch reads are named by its argument record, beside its fields (views(), onnx_graph.h); `out` comes
+// last.  F(Name, View&): the name is what the lifetimes dump prints (LifetimeTrace).
 template <class Fn> void forEachNamedView(Launch& L, Fn F) {
-    static const char* const SrcName[] = {"srcSame", "srcBoard", "", "", "", "srcRankLine", "srcFileLine", "srcLine", "srcRowOne", "srcBoardOne", ""};
-    F("in", L.in);
-    F("res", L.res);
-    F("attK", L.attK);
-    F("attV", L.attV);
-    F("rtBias", L.rtBias);
-    F("bmmB", L.bmmB);
-    for (EltSrc& S : L.srcs)
-        if (S.mode == kSrcSame || S.mode == kSrcBoard || (S.mode >= kSrcRankLine && S.mode != kSrcSquare)) F(SrcName[S.mode], S.v);
-    for (CopySeg& S : L.segs) F("seg", S.v);
+    std::visit([&](auto& A) { A.views(F); }, L.args);
     F("out", L.out);
 }
 template <class Fn> void forEachView(Launch& L, Fn F) {
@@ -266,8 +259,8 @@ class Planner {
     }
 
     void emit(Launch L) {
-        if (L.kind == kLaunchConv) ++P.convLaunches;
-        if (L.kind == kLaunchAttention) ++P.attentionLaunches;
+        if (L.is<ConvArgs>()) ++P.convLaunches;
+        if (L.is<AttentionArgs>()) ++P.attentionLaunches;
         P.launches.push_back(std::move(L));
     }
     void emitGroup(int Gi) {
@@ -275,12 +268,9 @@ class Planner {
         if (!Gr.open) return;
         Gr.open = false;
         Launch L;
-        L.kind = kLaunchElt;
         L.name = Gr.name;
         L.out = Gr.lines ? freshLines(Gr.C, Gr.lines) : freshView(Gr.C, Gr.spatial);
-        L.srcs = Gr.srcs;
-        L.code = Gr.code;
-        L.eltOut = Gr.outReg;
+        L.args = EltProgram{Gr.srcs, Gr.code, Gr.outReg};
         emit(L);
         Val& V = Vals[Gr.out];
         V.v = L.out;
@@ -292,25 +282,18 @@ class Planner {
         if (V.group >= 0) emitGroup(V.group);
         return Vals.at(Name);
     }
+    // a copy of view V in rows of its own: one kLaunchConcat of one segment
+    View copyOf(const View& V, bool Spatial, const std::string& Why) {
+        const View Out = freshView(V.C, Spatial);
+        emit(Launch{Why, Out, ConcatSegs{{CopySeg{V, 0}}}});
+        return Out;
+    }
     // a view with offset 0 in a buffer of its own kind (conv input, dense input, mean input)
     View plain(const std::string& Name, const std::string& Why) {
         const Val& V0 = ready(Name);
         if (!V0.flatOfSpatial && V0.v.offset == 0 && V0.v.stride == roundUp(V0.v.C, kChunk)) return V0.v;
-        Launch L;
-        L.name = Why;
-        if (V0.flatOfSpatial) {
-            L.kind = kLaunchFlatten;
-            L.in = V0.v;
-            L.out = freshView(V0.v.C * 81, false);
-        } else {
-            L.kind = kLaunchConcat;
-            CopySeg S;
-            S.v = V0.v;
-            L.segs.push_back(S);
-            L.out = freshView(V0.v.C, V0.v.spatial);
-        }
-        const View Out = L.out;
-        emit(L);
+        const View Out = V0.flatOfSpatial ? freshView(V0.v.C * 81, false) : copyOf(V0.v, V0.v.spatial, Why);
+        if (V0.flatOfSpatial) emit(Launch{Why, Out, FlattenArgs{V0.v}});
         Val& V = Vals[Name];
         V.v = Out;
         V.flatOfSpatial = false;

@@ -11,25 +11,24 @@ namespace nsg::graph {
 View Planner::gatherLaunch(const Node& N, const View& In, long Block, const std::vector<int>& RowTab,
                            const std::vector<int>& ColTab, bool Spatial) {
     Launch L;
-    L.kind = kLaunchGather;
     L.name = N.Name;
-    L.in = In;
-    L.res.buf = kNoRes;
+    GatherArgs& A = L.args.emplace<GatherArgs>();
+    A.in = In;
     L.out = freshView((int)ColTab.size(), Spatial);
-    L.gatherRows = (int)RowTab.size();
-    L.gatherBlock = Block;
+    A.gatherRows = (int)RowTab.size();
+    A.gatherBlock = Block;
     const int RowMin = *std::min_element(RowTab.begin(), RowTab.end()), RowMax = *std::max_element(RowTab.begin(), RowTab.end());
     const int ColMin = *std::min_element(ColTab.begin(), ColTab.end()), ColMax = *std::max_element(ColTab.begin(), ColTab.end());
-    if (L.gatherRows != (Spatial ? 81 : 1) || RowMin < 0 || ColMin < 0 || (long)RowMax + (long)ColMax >= Block)
+    if (A.gatherRows != (Spatial ? 81 : 1) || RowMin < 0 || ColMin < 0 || (long)RowMax + (long)ColMax >= Block)
         fail(N, "internal planner error: a gather table reaches outside its board's block");
     // rowTab[gatherRows], then colTab[out.stride] with pad entries 0, each 16-byte aligned, bit for bit in the float blob
-    const size_t RowInts = (size_t)roundUp(L.gatherRows, 4);
+    const size_t RowInts = (size_t)roundUp(A.gatherRows, 4);
     std::vector<int32_t> Tab(RowInts + (size_t)L.out.stride, 0);
     std::copy(RowTab.begin(), RowTab.end(), Tab.begin());
     std::copy(ColTab.begin(), ColTab.end(), Tab.begin() + (long)RowInts);
     std::vector<float> Tb(Tab.size());
     std::memcpy(Tb.data(), Tab.data(), Tab.size() * sizeof(int32_t));
-    L.gatherTabOff = addConst(Tb);
+    A.gatherTabOff = addConst(Tb);
     const View Out = L.out;
     emit(L);
     return Out;

@@ -250,34 +250,33 @@ void Planner::linear(const Node& N, size_t Index) {
     const int OutForm = Tok ? kFormToken : kFormPlain;
     const Epilogue E = foldEpilogue(N, Index, Dims, Tok ? 2 : 1, OutForm, &Lw);
     Launch L;
-    L.kind = kLaunchConv;
     L.name = E.name;
-    L.dense = Dense && !Tok;
-    L.depthwise = Lw.Depthwise;
-    L.taps = Lw.taps();
-    L.kh = Lw.KH;
-    L.kw = Lw.KW;
-    L.dh = Lw.DH;
-    L.dw = Lw.DW;
-    L.in = plain(N.In[0], N.Name + " (input copy)");
-    L.cinPad = roundUp(Lw.Cin, kChunk);
-    L.coutTiles = Lw.Depthwise ? 0 : (Cout + kCoutTile - 1) / kCoutTile;
-    L.act = E.act;
-    L.res.buf = kNoRes;
-    if (!E.res.empty()) L.res = ready(E.res).v;
+    ConvArgs& A = L.args.emplace<ConvArgs>();
+    A.dense = Dense && !Tok;
+    A.depthwise = Lw.Depthwise;
+    A.taps = Lw.taps();
+    A.kh = Lw.KH;
+    A.kw = Lw.KW;
+    A.dh = Lw.DH;
+    A.dw = Lw.DW;
+    A.in = plain(N.In[0], N.Name + " (input copy)");
+    A.cinPad = roundUp(Lw.Cin, kChunk);
+    A.coutTiles = Lw.Depthwise ? 0 : (Cout + kCoutTile - 1) / kCoutTile;
+    A.act = E.act;
+    if (!E.res.empty()) A.res = ready(E.res).v;
     std::vector<float> Pk, Bf, Tb;
-    if (Lw.Depthwise) packDepthwise(Lw, L.cinPad / kChunk, &Pk, &Bf);
-    else if (Lw.Groups > 1) packGrouped(Lw, L.coutTiles, &Pk, &Tb, &Bf);
-    else packDense(Lw, L.cinPad / kChunk, L.coutTiles, &Pk, &Bf);
+    if (Lw.Depthwise) packDepthwise(Lw, A.cinPad / kChunk, &Pk, &Bf);
+    else if (Lw.Groups > 1) packGrouped(Lw, A.coutTiles, &Pk, &Tb, &Bf);
+    else packDense(Lw, A.cinPad / kChunk, A.coutTiles, &Pk, &Bf);
     if (Pk.size() > (size_t)INT32_MAX) fail(N, "the packed weights exceed 2^31 floats");
-    L.wOff = addConst(Pk);
-    L.biasOff = addConst(Bf);
+    A.wOff = addConst(Pk);
+    A.biasOff = addConst(Bf);
     if (Lw.Groups > 1) { // the tables are constants of grouped launches only: every other plan keeps its blob
-        L.groups = Lw.Groups;
-        L.gTabOff = addConst(Tb);
+        A.groups = Lw.Groups;
+        A.gTabOff = addConst(Tb);
     }
-    L.out = freshView(Cout, !L.dense);
-    P.flopsPerPosition += 2.0 * (L.dense ? 1 : 81) * L.taps * (double)Lw.CinW * Cout;
+    L.out = freshView(Cout, !A.dense);
+    P.flopsPerPosition += 2.0 * (A.dense ? 1 : 81) * A.taps * (double)Lw.CinW * Cout;
     Val V = runtimeVal(N, Dims, OutForm);
     V.v = L.out;
     V.producer = N.Name;
@@ -297,20 +296,19 @@ void Planner::headRowsDense(const Node& N, size_t Index) {
     const std::vector<int64_t> Dims{kBatch, H, Cout};
     const Epilogue E = foldEpilogue(N, Index, Dims, 2, -1, &Lw);
     Launch L;
-    L.kind = kLaunchConv;
     L.name = E.name;
-    L.dense = true;
-    L.rowsPerBoard = H;
-    L.taps = L.kh = L.kw = 1;
-    L.in = X.v;
-    L.cinPad = roundUp(Lw.Cin, kChunk);
-    L.coutTiles = (Cout + kCoutTile - 1) / kCoutTile;
-    L.act = E.act;
-    L.res.buf = kNoRes;
+    ConvArgs& A = L.args.emplace<ConvArgs>();
+    A.dense = true;
+    A.rowsPerBoard = H;
+    A.taps = A.kh = A.kw = 1;
+    A.in = X.v;
+    A.cinPad = roundUp(Lw.Cin, kChunk);
+    A.coutTiles = (Cout + kCoutTile - 1) / kCoutTile;
+    A.act = E.act;
     std::vector<float> Pk, Bf;
-    packDense(Lw, L.cinPad / kChunk, L.coutTiles, &Pk, &Bf);
-    L.wOff = addConst(Pk);
-    L.biasOff = addConst(Bf);
+    packDense(Lw, A.cinPad / kChunk, A.coutTiles, &Pk, &Bf);
+    A.wOff = addConst(Pk);
+    A.biasOff = addConst(Bf);
     L.out.stride = roundUp(Cout, kChunk);
     L.out.C = Cout;
     L.out.spatial = false;
@@ -364,25 +362,14 @@ void Planner::bmm(const Node& N, size_t Index) {
     auto operand = [&](const std::string& Name) {
         const View V0 = ready(Name).v;
         if (V0.offset % 4 == 0) return V0;
-        Launch L;
-        L.kind = kLaunchConcat;
-        L.name = N.Name + " (input copy)";
-        CopySeg S;
-        S.v = V0;
-        L.segs.push_back(S);
-        L.out = freshView(V0.C, true);
-        const View Out = L.out;
-        emit(L);
-        Vals[Name].v = Out;
-        return Out;
+        return Vals[Name].v = copyOf(V0, true, N.Name + " (input copy)");
     };
     Launch L;
-    L.kind = kLaunchBmm;
-    L.in = operand(N.In[0]);
-    L.bmmB = operand(N.In[1]);
-    L.bmmNN = NN;
-    L.bmmK = (int)Inner;
-    L.res.buf = kNoRes;
+    BmmArgs& A = L.args.emplace<BmmArgs>();
+    A.in = operand(N.In[0]);
+    A.bmmB = operand(N.In[1]);
+    A.bmmNN = NN;
+    A.bmmK = (int)Inner;
     const int Cout = NN ? (int)B0.dims[2] : 81;
     // the epilogue: constant scalar Mul / Div nodes, then at most one parameter-free activation
     std::string Name = N.Name, Cur = N.Out[0];
@@ -396,7 +383,7 @@ void Planner::bmm(const Node& N, size_t Index) {
             (C->In[0] == Cur || C->Op == "Mul") && scalarAhead(C->In[0] == Cur ? C->In[1] : C->In[0], &S)) {
             Scale = C->Op == "Mul" ? Scale * S : Scale / S;
         } else if (!C->In.empty() && C->In[0] == Cur && nodeAct(*C) != kActNone) {
-            L.act = nodeAct(*C);
+            A.act = nodeAct(*C);
         } else {
             break;
         }
@@ -404,10 +391,10 @@ void Planner::bmm(const Node& N, size_t Index) {
         Skip[indexOf(C)] = true;
         At = indexOf(C);
         Cur = C->Out[0];
-        if (L.act != kActNone) break;
+        if (A.act != kActNone) break;
     }
     L.name = Name;
-    L.scale = (float)Scale;
+    A.scale = (float)Scale;
     L.out = freshView(Cout, true);
     P.flopsPerPosition += 2.0 * 81 * 81 * (double)(NN ? Cout : Inner);
     Val V = runtimeVal(N, {kBatch, 81, Cout}, kFormToken);

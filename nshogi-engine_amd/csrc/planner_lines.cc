@@ -10,11 +10,9 @@ void Planner::linePool(const Node& N, bool Files, bool Max) {
     const Val& X = get(N, 0);
     const int C = (int)X.dims[1];
     Launch L;
-    L.kind = kLaunchLinePool;
     L.name = N.Name;
-    L.poolMode = Max ? kPoolMax : kPoolAvgInclude;
-    L.lineFiles = Files;
-    L.in = ready(N.In[0]).v; // a view at any channel offset, read where it lies
+    const View In = ready(N.In[0]).v; // a view at any channel offset, read where it lies
+    L.args = LinePoolArgs{In, Files, Max ? kPoolMax : kPoolAvgInclude};
     L.out = freshLines(C, 9);
     Val V;
     V.runtime = true;
@@ -31,18 +29,11 @@ void Planner::linePool(const Node& N, bool Files, bool Max) {
 View Planner::linePlain(const std::string& Name, const std::string& Why) {
     const View V0 = ready(Name).v;
     if (V0.offset == 0 && V0.stride == roundUp(V0.C, kChunk) && V0.line0 == 0 && V0.bufLines == V0.lines) return V0;
-    Launch L;
-    L.kind = kLaunchElt;
-    L.name = Why;
-    L.out = freshLines(V0.C, V0.lines);
+    const View Out = freshLines(V0.C, V0.lines);
     EltSrc S;
     S.v = V0;
     S.mode = V0.line0 != 0 || V0.bufLines != V0.lines ? kSrcLine : kSrcSame;
-    L.srcs.push_back(S);
-    L.code.push_back(EltInstr{(uint8_t)kEltLoad, 0, 0, 0});
-    L.eltOut = 0;
-    const View Out = L.out;
-    emit(L);
+    emit(Launch{Why, Out, EltProgram{{S}, {EltInstr{(uint8_t)kEltLoad, 0, 0, 0}}, 0}});
     Val& V = Vals[Name];
     V.v = Out;
     V.lineLaunch = -1;
@@ -83,26 +74,25 @@ void Planner::lineConv(const Node& N, size_t Index) {
     // BatchNorm, constant per-channel Adds and one activation; a residual is not absorbed (it stays an elementwise Add)
     const Epilogue E = foldEpilogue(N, Index, Dims, 1, -1, &Lw);
     Launch L;
-    L.kind = kLaunchConv;
     L.name = E.name;
-    L.dense = true;
-    L.rowsPerBoard = Ln;
-    L.taps = L.kh = L.kw = 1;
-    L.in = linePlain(N.In[0], N.Name + " (input copy)");
-    L.cinPad = roundUp(Lw.Cin, kChunk);
-    L.coutTiles = (Cout + kCoutTile - 1) / kCoutTile;
-    L.act = E.act;
-    L.res.buf = kNoRes;
+    ConvArgs& A = L.args.emplace<ConvArgs>();
+    A.dense = true;
+    A.rowsPerBoard = Ln;
+    A.taps = A.kh = A.kw = 1;
+    A.in = linePlain(N.In[0], N.Name + " (input copy)");
+    A.cinPad = roundUp(Lw.Cin, kChunk);
+    A.coutTiles = (Cout + kCoutTile - 1) / kCoutTile;
+    A.act = E.act;
     // packed [tile][chunk][1][16][64], bias [tiles * 64]
-    const int Chunks = L.cinPad / kChunk;
-    std::vector<float> Pk((size_t)L.coutTiles * Chunks * kChunk * kCoutTile, 0.f), Bf((size_t)L.coutTiles * kCoutTile, 0.f);
+    const int Chunks = A.cinPad / kChunk;
+    std::vector<float> Pk((size_t)A.coutTiles * Chunks * kChunk * kCoutTile, 0.f), Bf((size_t)A.coutTiles * kCoutTile, 0.f);
     for (int O = 0; O < Cout; ++O) {
         for (int I = 0; I < Lw.Cin; ++I)
             Pk[(((size_t)(O / kCoutTile) * Chunks + I / kChunk) * kChunk + I % kChunk) * kCoutTile + O % kCoutTile] = (float)Lw.W[(size_t)O * Lw.Cin + I];
         Bf[(size_t)O] = (float)Lw.Bias[(size_t)O];
     }
-    L.wOff = addConst(Pk);
-    L.biasOff = addConst(Bf);
+    A.wOff = addConst(Pk);
+    A.biasOff = addConst(Bf);
     L.out = freshLines(Cout, Ln);
     P.flopsPerPosition += 2.0 * Ln * (double)Lw.Cin * Cout;
     Val V;

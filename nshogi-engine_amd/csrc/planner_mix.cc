@@ -139,28 +139,16 @@ void Planner::tokenMix(const Node& N, size_t Index) {
     }
 
     Launch L;
-    L.kind = kLaunchTokenMix;
     L.name = Name;
+    TokenMixArgs& A = L.args.emplace<TokenMixArgs>();
     // a view at a multiple of 4 is read where it lies, any other is copied into rows of its own first
-    L.in = ready(N.In[0]).v;
-    if (L.in.offset % 4 != 0) {
-        Launch Cp;
-        Cp.kind = kLaunchConcat;
-        Cp.name = N.Name + " (input copy)";
-        CopySeg Sg;
-        Sg.v = L.in;
-        Cp.segs.push_back(Sg);
-        Cp.out = freshView(L.in.C, true);
-        L.in = Cp.out;
-        emit(Cp);
-        Vals[N.In[0]].v = L.in;
-    }
-    L.res.buf = kNoRes;
-    L.wOff = addConst(Rec);
-    L.mixD = D;
-    L.mixStages = Two ? 2 : 1;
-    L.act = St[0].act;
-    L.mixAct2 = Two ? St[1].act : kActNone;
+    A.in = ready(N.In[0]).v;
+    if (A.in.offset % 4 != 0) Vals[N.In[0]].v = A.in = copyOf(A.in, true, N.Name + " (input copy)");
+    A.wOff = addConst(Rec);
+    A.mixD = D;
+    A.mixStages = Two ? 2 : 1;
+    A.act = St[0].act;
+    A.mixAct2 = Two ? St[1].act : kActNone;
     L.out = freshView((int)C, true);
     P.flopsPerPosition += 2.0 * 81 * (double)D * (double)C * (Two ? 2.0 : 1.0);
     Val V = X0;

@@ -25,13 +25,13 @@ void Planner::layerNorm(const Node& N) {
     }
     if (N.Out.size() > 1 && !N.Out[1].empty() && Uses.count(N.Out[1])) fail(N, "the mean / inverse-deviation outputs are not supported");
     Launch L;
-    L.kind = kLaunchLayerNorm;
     L.name = N.Name;
-    L.in = ready(N.In[0]).v;
+    LayerNormArgs& A = L.args.emplace<LayerNormArgs>();
+    A.in = ready(N.In[0]).v;
     L.out = freshView(C, Tok);
-    L.wOff = addConst(Gm);
-    L.biasOff = addConst(Bt);
-    L.eps = (float)N.attrF("epsilon", 1e-5);
+    A.wOff = addConst(Gm);
+    A.biasOff = addConst(Bt);
+    A.eps = (float)N.attrF("epsilon", 1e-5);
     Val V = runtimeVal(N, X.dims, X.form);
     V.v = L.out;
     emit(L);
@@ -81,14 +81,14 @@ void Planner::groupNorm(const Node& Last, size_t Index, const View& In, int C, i
         Cur = Nx->Out[0];
     }
     Launch L;
-    L.kind = kLaunchGroupNorm;
     L.name = Name;
-    L.in = In; // a view at any channel offset: the kernel reads it where it lies
-    L.groups = G;
-    L.act = Act;
-    L.eps = (float)Eps;
-    L.wOff = addConst(std::vector<float>(Gm.begin(), Gm.end()));
-    L.biasOff = addConst(std::vector<float>(Bt.begin(), Bt.end()));
+    GroupNormArgs& Ga = L.args.emplace<GroupNormArgs>();
+    Ga.in = In; // a view at any channel offset: the kernel reads it where it lies
+    Ga.groups = G;
+    Ga.act = Act;
+    Ga.eps = (float)Eps;
+    Ga.wOff = addConst(std::vector<float>(Gm.begin(), Gm.end()));
+    Ga.biasOff = addConst(std::vector<float>(Bt.begin(), Bt.end()));
     L.out = freshView(C, true);
     Val V = runtimeVal(Last, Dims);
     V.v = L.out;
@@ -202,17 +202,16 @@ bool Planner::decomposedNorm(const Node& N, size_t Index) {
     affine("Mul", Gm);
     if (Mean) affine("Add", Bt);
     Launch L;
-    L.kind = Mean ? kLaunchLayerNorm : kLaunchRmsNorm;
     L.name = N.Name;
     for (const Node* A : Absorbed) {
         L.name += "+" + A->Name;
         Skip[indexOf(A)] = true;
     }
-    L.in = ready(N.In[0]).v;
+    const View In = ready(N.In[0]).v;
     L.out = freshView(C, X0.form != kFormPlain);
-    L.wOff = addConst(Gm);
-    if (Mean) L.biasOff = addConst(Bt);
-    L.eps = (float)Eps;
+    const size_t WOff = addConst(Gm);
+    if (Mean) L.args = LayerNormArgs{In, WOff, addConst(Bt), (float)Eps};
+    else L.args = RmsNormArgs{In, WOff, (float)Eps};
     Val V = runtimeVal(*Y, X0.dims, X0.form);
     V.v = L.out;
     emit(L);

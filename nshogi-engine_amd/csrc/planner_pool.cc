@@ -25,8 +25,7 @@ void Planner::pool(const Node& N) {
     L.name = N.Name;
     if (Max && Ks == std::vector<int64_t>{9, 9} && Pads == std::vector<int64_t>{0, 0, 0, 0} && Dil == std::vector<int64_t>{1, 1} &&
         !Ceil && !AutoPad) { // one window: the strides do not matter
-        L.kind = kLaunchMax;
-        L.in = ready(N.In[0]).v;
+        L.args = SquareReduceArgs{ready(N.In[0]).v, true};
         L.out = freshView(C, false);
         Val V = runtimeVal(N, {kBatch, C, 1, 1});
         V.v = L.out;
@@ -62,13 +61,9 @@ void Planner::pool(const Node& N) {
         fail(N, "pads [" + Ps + "] do not keep the 9x9 board: a " + KStr + " kernel at dilation " + std::to_string(DH) + "x" +
                     std::to_string(DW) + " needs [" + std::to_string(Hy) + "," + std::to_string(Hx) + "," + std::to_string(Hy) + "," + std::to_string(Hx) + "]");
     }
-    L.kind = kLaunchPool;
-    L.kh = KH;
-    L.kw = KW;
-    L.dh = DH;
-    L.dw = DW;
-    L.poolMode = Max ? kPoolMax : N.attrI("count_include_pad", 0) != 0 ? kPoolAvgInclude : kPoolAvgExclude;
-    L.in = ready(N.In[0]).v; // a view at any channel offset: the kernel reads an unaligned one with scalar loads
+    const int Mode = Max ? kPoolMax : N.attrI("count_include_pad", 0) != 0 ? kPoolAvgInclude : kPoolAvgExclude;
+    // a view at any channel offset: the kernel reads an unaligned one with scalar loads
+    L.args = PoolArgs{ready(N.In[0]).v, KH, KW, DH, DW, Mode};
     L.out = freshView(C, true);
     Val V = runtimeVal(N, X.dims);
     V.v = L.out;
@@ -100,9 +95,8 @@ void Planner::reduceSquares(const Node& N) {
     }
     const int C = Tok ? (int)X.dims[2] : (int)X.dims[1];
     Launch L;
-    L.kind = Op == "GlobalMaxPool" || Op == "ReduceMax" ? kLaunchMax : kLaunchMean;
     L.name = N.Name;
-    L.in = ready(N.In[0]).v;
+    L.args = SquareReduceArgs{ready(N.In[0]).v, Op == "GlobalMaxPool" || Op == "ReduceMax"};
     L.out = freshView(C, false);
     Val V = runtimeVal(N, Keep ? std::vector<int64_t>{kBatch, C, 1, 1} : std::vector<int64_t>{kBatch, C});
     V.v = L.out;
@@ -139,13 +133,13 @@ void Planner::reduceChannels(const Node& N) {
                     "; a reduction over the channels keeps the axis (keepdims = 1)");
     const int C = Kind == 2 ? (int)XD[2] : (int)XD[1];
     Launch L;
-    L.kind = kLaunchChanReduce;
     L.name = N.Name;
-    L.redMode = Op == "ReduceMax" ? kRedMax : Op == "ReduceMin" ? kRedMin : kRedSum;
-    L.scale = Op == "ReduceMean" ? (float)(1.0 / C) : 1.f; // the mean: the sum times the f32 constant 1/C, applied after the last add
-    L.in = ready(N.In[0]).v; // a view at any channel offset: the kernel reads the ragged ends with scalar loads
+    ChanReduceArgs& A = L.args.emplace<ChanReduceArgs>();
+    A.redMode = Op == "ReduceMax" ? kRedMax : Op == "ReduceMin" ? kRedMin : kRedSum;
+    A.scale = Op == "ReduceMean" ? (float)(1.0 / C) : 1.f; // the mean: the sum times the f32 constant 1/C, applied after the last add
+    A.in = ready(N.In[0]).v; // a view at any channel offset: the kernel reads the ragged ends with scalar loads
     L.out = freshView(1, Kind != 3);
-    if (L.redMode == kRedSum) P.flopsPerPosition += (double)C * (Kind == 3 ? 1 : 81);
+    if (A.redMode == kRedSum) P.flopsPerPosition += (double)C * (Kind == 3 ? 1 : 81);
     std::vector<int64_t> OD = XD;
     OD[Kind == 2 ? 2 : 1] = 1;
     Val V = runtimeVal(N, OD, Kind == 2 ? kFormToken : kFormPlain);

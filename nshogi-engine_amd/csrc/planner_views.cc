@@ -278,24 +278,24 @@ Val Planner::headsSource(const Node& N, const Val& X0) {
 void Planner::attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND) {
     const int64_t H = X0.dims[2], Hd = X0.dims[3];
     Launch L;
-    L.kind = kLaunchAttention;
     L.name = X0.chain + "+" + N.Name;
-    L.in = X0.attQ;
-    L.attK = X0.attK;
-    L.attV = X0.attV;
-    L.heads = (int)H;
-    L.headDim = (int)Hd;
-    L.scale = (float)X0.scale;
-    L.hasBias = !X0.bias.empty();
-    if (L.hasBias) {
+    AttentionArgs& A = L.args.emplace<AttentionArgs>();
+    A.in = X0.attQ;
+    A.attK = X0.attK;
+    A.attV = X0.attV;
+    A.heads = (int)H;
+    A.headDim = (int)Hd;
+    A.scale = (float)X0.scale;
+    A.hasBias = !X0.bias.empty();
+    if (A.hasBias) {
         std::vector<float> Bf(X0.bias.begin(), X0.bias.end());
-        L.biasOff = addConst(Bf);
+        A.biasOff = addConst(Bf);
     }
-    L.hasRtBias = X0.hasRt;
-    if (L.hasRtBias) {
-        L.rtBias = X0.rtBias;
-        L.rtHeadStride = X0.rtHead;
-        L.rtScale = (float)X0.rtScale;
+    A.hasRtBias = X0.hasRt;
+    if (A.hasRtBias) {
+        A.rtBias = X0.rtBias;
+        A.rtHeadStride = X0.rtHead;
+        A.rtScale = (float)X0.rtScale;
     }
     L.out = freshView((int)(H * Hd), true);
     P.flopsPerPosition += 2.0 * (2.0 * 81 * 81 * (double)Hd) * (double)H; // q k^T and probs x v
@@ -508,8 +508,8 @@ void Planner::concat(const Node& N) {
     if (Ax != 1) fail(N, "Concat of runtime tensors along axis 1 only");
     if (N.In.size() > (size_t)kMaxCopySegs) fail(N, "more than " + std::to_string(kMaxCopySegs) + " inputs");
     Launch L;
-    L.kind = kLaunchConcat;
     L.name = N.Name;
+    std::vector<CopySeg>& Segs = L.args.emplace<ConcatSegs>().segs;
     int Total = 0;
     bool Sp = false;
     for (size_t J = 0; J < N.In.size(); ++J) {
@@ -524,7 +524,7 @@ void Planner::concat(const Node& N) {
         S.v = V.flatOfSpatial ? plain(N.In[J], N.Name + " (flatten)") : ready(N.In[J]).v;
         S.dstOff = Total;
         Total += S.v.C;
-        L.segs.push_back(S);
+        Segs.push_back(S);
     }
     L.out = freshView(Total, Sp);
     std::vector<int64_t> ND = Sp ? std::vector<int64_t>{kBatch, Total, 9, 9} : std::vector<int64_t>{kBatch, Total};
