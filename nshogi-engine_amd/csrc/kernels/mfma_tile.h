@@ -1,6 +1,6 @@
 // mfma_tile.h -- the MFMA tile kernel behind every contraction of the
 // policy/value/draw network on gfx950 (CDNA4).  Included by the per-precision
-// translation units mfma_tile_{fp32,fp16,bf16,f16x3,f16m8}.hip.
+// translation units mfma_tile_{fp32,fp16,bf16,f16x3,f16m8,f16m6}.hip.
 //
 // It is the body of the opaque TensorRT engine the reference enqueues at
 // src/infer/trt.cc:261 (F1 in SURVEY.md 2b; a7 in 8a).  Nothing here is
@@ -1522,13 +1522,17 @@ _Pragma("unroll") \
             resRs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(resBase), 0, 0x7fffffff, 0x00027000);
             yRs = __builtin_amdgcn_make_buffer_rsrc(yBase, 0, 0x7fffffff, 0x00027000);
         }
+        // (a persistent trunk reads its layer list from memory: those pointers are generic to the compiler, and a flat_
+        // access costs a 64-bit per-lane address (v_lshl_add_u64) and counts against the LDS counter as well.  Activations
+        // are global memory: said so, the accesses are global_ ones on a scalar base + a 32-bit lane offset.)
+        typedef __attribute__((address_space(1))) u32x4 gu32x4;
         auto resLoad = [&](size_t off_) -> u32x4 {
             if constexpr (COOP) return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(resRs, (int)off_, 0, 16));
-            else return *reinterpret_cast<const u32x4*>(resBase + off_);
+            else return *(const gu32x4*)(unsigned long long)(resBase + off_);
         };
         auto outStore = [&](size_t off_, const u32x4& v_) {
             if constexpr (COOP) __builtin_amdgcn_raw_buffer_store_b128(v_, yRs, (int)off_, 0, kCoopSameXcd ? 0 : 16);
-            else *reinterpret_cast<u32x4*>(yBase + off_) = v_;
+            else *(gu32x4*)(unsigned long long)(yBase + off_) = v_;
         };
         // edge-packed rows: per-lane offsets of the four rows (it = 0..3) this lane moves for fragment f
         [[maybe_unused]] const unsigned permLane = (unsigned)lpc * 16u;
@@ -1652,10 +1656,25 @@ _Pragma("unroll") \
             if (i >= 0 && i < kMFe) { // ---- X(i)
                 const int f = i;
                 float v[NFRAG * 4];
+                if constexpr (kM6) {
+                    // two values per v_pk_fma_f32, the same single-rounded fma per value (left to itself the compiler packs
+                    // these only where a packed consumer follows: the residual body's v_pk_add_f32)
+                    typedef float f32x2p __attribute__((ext_vector_type(2)));
 #pragma unroll
-                for (int j = 0; j < NFRAG; ++j)
+                    for (int j = 0; j < NFRAG; ++j)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[j * 4 + r] = fmaf(acc[f][j][r], A.accScale, bv[j * 4 + r]);
+                        for (int r = 0; r < 4; r += 2) {
+                            const f32x2p t = __builtin_elementwise_fma(f32x2p{acc[f][j][r], acc[f][j][r + 1]}, f32x2p{A.accScale, A.accScale},
+                                                                       f32x2p{bv[j * 4 + r], bv[j * 4 + r + 1]});
+                            v[j * 4 + r] = t[0];
+                            v[j * 4 + r + 1] = t[1];
+                        }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < NFRAG; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[j * 4 + r] = fmaf(acc[f][j][r], A.accScale, bv[j * 4 + r]);
+                }
                 [[maybe_unused]] unsigned char* lrowp = ebuf + (f % kRegions) * kFragBytes + li * kRowS;
                 if (hasRes) {
                     const u32x4* rp = rpp[f & 1];
@@ -1682,8 +1701,14 @@ _Pragma("unroll") \
                         typedef unsigned u32x6 __attribute__((ext_vector_type(6)));
                         typedef unsigned u32x16 __attribute__((ext_vector_type(16)));
                         const bool odd = (g & 1) != 0;
-                        const uint32_t c0 = odd ? rp[2].w : rp[2].x, c1 = odd ? rp[3].x : rp[2].y, c2 = odd ? rp[3].y : rp[2].z;
-                        const u32x6 blk = {c0, c1, c2, c0, c1, c2};
+                        // (c0's two candidates are elements of ONE vector: left to itself the compiler selects the element
+                        // INDEX and extracts by it -- three compares and three selects; the copy of .w hides that)
+                        uint32_t c0w = rp[2].w;
+                        asm("" : "+v"(c0w));
+                        const uint32_t c0 = odd ? c0w : rp[2].x, c1 = odd ? rp[3].x : rp[2].y, c2 = odd ? rp[3].y : rp[2].z;
+                        // (the upper three dwords -- values 16..31, never taken -- stay undefined: no copies to fill them)
+                        const u32x4 c012 = {c0, c1, c2, 0u};
+                        const u32x6 blk = __builtin_shufflevector(c012, c012, 0, 1, 2, -1, -1, -1);
                         const float sc = __uint_as_float((rp[3].z & 0xffu) << 23);
                         u32x16 lh;
                         asm("v_cvt_scalef32_pk32_f16_fp6 %0, %1, %2" : "=&v"(lh) : "v"(blk), "v"(sc));
@@ -1733,6 +1758,16 @@ _Pragma("unroll") \
                 }
                 u32x4 op[kNP];
                 [[maybe_unused]] const float floorV = A.relu ? 0.f : -65000.f;
+                // where this lane's k-th result piece goes in the image (an encoder may store its pieces as they become ready)
+                auto pieceAddr = [&](int k) -> unsigned char* {
+                    const int po = __builtin_expect(outX3, false) ? pieceOffX3(k) : pieceOff(k);
+                    if constexpr (KEEP) return stageAt(f, 1, 0, po / 16);
+                    else return lrowp + po;
+                };
+                auto storePiece = [&](int k, const u32x4& p_) { *reinterpret_cast<u32x4*>(pieceAddr(k)) = p_; };
+                // (a flag in front of the common store loop, not stores at the end of every encoder arm: that form made the
+                // f16m8 slab-split tiles spill 5 and 3 registers)
+                [[maybe_unused]] bool stored = false;
                 if constexpr (PREC == kFp32) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -1775,13 +1810,15 @@ _Pragma("unroll") \
                         // (scalars in plain arrays, vectors built by initialiser lists: element-wise writes to a
                         // 16-wide ext_vector in this loop compiled to compare/select chains, 2400 extra instructions)
                         typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-                        uint32_t hpv[8], sa[8], sb[8];
+                        uint32_t hpv[8], lpv[8], sa[8], sb[8];
                         // running maxima of |x| and |x - hi| in f32, one v_max3_f32 with |.| modifiers per pair: rounding to
                         // f16 is monotonic, so the f16 of the maximum IS the maximum of the f16 values the block stores
                         // (masking the packed f16 pairs and taking packed integer maxima was four instructions per pair)
                         float mh = 0.f, ml = 0.f;
-                        float mone = -1.0f;
-                        asm("" : "+v"(mone));
+                        // (its own 1.0, not the decoder's kept alive in between: that register costs the one-wave
+                        // two-board tile a spill)
+                        float one = 1.0f;
+                        asm("" : "+v"(one));
                         (void)sizeof(u16x2);
 #pragma unroll
                         for (int d = 0; d < 8; ++d) {
@@ -1789,24 +1826,38 @@ _Pragma("unroll") \
                                              __builtin_amdgcn_fmed3f(v[2 * d + 1], floorV, 65000.f)};
                             const f16x2 h = __builtin_convertvector(x, f16x2);
                             const uint32_t hp = __builtin_bit_cast(uint32_t, h);
-                            // lo = x - hi as ONE v_fma_mix_f32 per value: the f16 half of `hp` is converted on the fly (written
-                            // as (float)h[i] the compiler emitted a v_cvt_f32_f16 per value in front of a plain fma)
+                            // lo = x - hi as ONE v_fma_mix_f32 per value, -hi * 1.0 + x: the f16 half of `hp` is converted on the
+                            // fly (written as (float)h[i] the compiler emitted a v_cvt_f32_f16 per value in front of a plain fma)
                             f32x2 lx;
-                            asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(lx[0]) : "v"(hp), "v"(mone), "v"(x[0]));
-                            asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(lx[1]) : "v"(hp), "v"(mone), "v"(x[1]));
-                            const uint32_t lp = __builtin_bit_cast(uint32_t, __builtin_convertvector(lx, f16x2));
+                            asm("v_fma_mix_f32 %0, -%1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(lx[0]) : "v"(hp), "v"(one), "v"(x[0]));
+                            asm("v_fma_mix_f32 %0, -%1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(lx[1]) : "v"(hp), "v"(one), "v"(x[1]));
                             hpv[d] = hp;
+                            lpv[d] = __builtin_bit_cast(uint32_t, __builtin_convertvector(lx, f16x2));
                             mh = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(x[0]), __builtin_fabsf(x[1])), mh);
                             ml = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(lx[0]), __builtin_fabsf(lx[1])), ml);
-                            const u32x2v sw = __builtin_amdgcn_permlane16_swap(hp, lp, false, false);
+                        }
+                        // The hi pieces leave for the image BEFORE the swaps: v_permlane16_swap works in place, and with hi
+                        // still wanted behind it every swap needed a copy of its hi operand first (8 v_mov per fragment).
+                        // (Not in the one-wave tiles: their two-board form is out of registers, and the early store costs
+                        // it one more spilled register.)
+                        constexpr bool kHiFirst = NWAVES > 1;
+                        if constexpr (kHiFirst) {
+                            storePiece(0, u32x4{hpv[0], hpv[1], hpv[2], hpv[3]});
+                            storePiece(1, u32x4{hpv[4], hpv[5], hpv[6], hpv[7]});
+                        }
+#pragma unroll
+                        for (int d = 0; d < 8; ++d) {
+                            const u32x2v sw = __builtin_amdgcn_permlane16_swap(hpv[d], lpv[d], false, false);
                             sa[d] = sw.x;
                             sb[d] = sw.y;
+                        }
+                        if constexpr (!kHiFirst) {
+                            storePiece(0, u32x4{hpv[0], hpv[1], hpv[2], hpv[3]});
+                            storePiece(1, u32x4{hpv[4], hpv[5], hpv[6], hpv[7]});
                         }
                         // f16 bit pattern -> E8M0: f16 exponent field e5 (bias 15) is the float exponent e5 + 112
                         const uint32_t mbits = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{mh, ml}, f16x2));
                         const uint32_t mhb = mbits & 0xffffu, mlb = mbits >> 16;
-                        op[0] = u32x4{hpv[0], hpv[1], hpv[2], hpv[3]};
-                        op[1] = u32x4{hpv[4], hpv[5], hpv[6], hpv[7]};
                         const u32x16 src = {sa[0], sa[1], sa[2], sa[3], sa[4], sa[5], sa[6], sa[7],
                                             sb[0], sb[1], sb[2], sb[3], sb[4], sb[5], sb[6], sb[7]};
                         const u32x2v mm = __builtin_amdgcn_permlane16_swap(mhb, mlb, false, false);
@@ -1815,8 +1866,14 @@ _Pragma("unroll") \
                         u32x6 blk;
                         const float sc = __uint_as_float(e8 << 23);
                         asm("v_cvt_scalef32_pk32_fp6_f16 %0, %1, %2" : "=&v"(blk) : "v"(src), "v"(sc));
-                        op[2] = u32x4{blk.s0, blk.s1, blk.s2, blk.s3};
-                        op[3] = u32x4{blk.s4, blk.s5, e8, e8}; // (the exponent twice: the consumer's split read, kSplitRead)
+                        // the code dwords go out of the conversion's own register tuple (16 + 8 bytes), the exponent twice
+                        // (the consumer's split read, kSplitRead) from its one register: no [s4, s5, e8, e8] vector to assemble
+                        storePiece(2, __builtin_shufflevector(blk, blk, 0, 1, 2, 3));
+                        unsigned char* p3 = pieceAddr(3);
+                        *reinterpret_cast<u32x2v*>(p3) = __builtin_shufflevector(blk, blk, 4, 5);
+                        reinterpret_cast<uint32_t*>(p3)[2] = e8;
+                        reinterpret_cast<uint32_t*>(p3)[3] = e8;
+                        stored = true;
                     } else {
                         // two values per instruction where the ISA has a packed form (v_cvt_pk_f16_f32,
                         // v_pk_add_f32, v_pk_mul_f32); v_med3 needs no NaN-quieting of its inputs
@@ -1851,10 +1908,9 @@ _Pragma("unroll") \
 #pragma unroll
                         for (int i = 0; i < 4; ++i) op[k][i] = packPair<PREC>(v[k * 8 + 2 * i], v[k * 8 + 2 * i + 1]);
                 }
+                if (!stored) {
 #pragma unroll
-                for (int k = 0; k < kNP; ++k) {
-                    if constexpr (KEEP) *reinterpret_cast<u32x4*>(stageAt(f, 1, 0, (__builtin_expect(outX3, false) ? pieceOffX3(k) : pieceOff(k)) / 16)) = op[k];
-                    else *reinterpret_cast<u32x4*>(lrowp + (__builtin_expect(outX3, false) ? pieceOffX3(k) : pieceOff(k))) = op[k];
+                    for (int k = 0; k < kNP; ++k) storePiece(k, op[k]);
                 }
             }
             if (i >= 1) { // ---- S(i-1), stores: kRPI rows x kRowB contiguous bytes per instruction
