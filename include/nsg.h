@@ -124,8 +124,14 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    the tokens flattened to [N,81*C] (C a multiple of 16), dense layers, an
  *    optional [N,H,K] stage with one Linear shared by the heads (K a multiple of
  *    16), and a Reshape into the scores' shape; the attention still is one
- *    launch.  A mask input and nn.MultiheadAttention's own export form stay
- *    refused.  Outside that pattern a MatMul of two run-time token tensors is
+ *    launch.  PyTorch's stock modules load as exported: nn.MultiheadAttention
+ *    doing self-attention over the 81 squares (batch_first or not, with or
+ *    without biases, need_weights False or True with the weights unused),
+ *    nn.TransformerEncoderLayer (pre- or post-norm, relu or gelu) and
+ *    nn.TransformerEncoder plan to the launches of the hand-written form.
+ *    A mask (attn_mask, key_padding_mask, is_causal), attention weights that
+ *    are used, kdim / vdim other than embed_dim, add_bias_kv, add_zero_attn
+ *    and cross-attention stay refused.  Outside that pattern a MatMul of two run-time token tensors is
  *    one launch of its own: [N,81,K] x [N,K,81] (an attention policy head's
  *    from . to^T, a Gram matrix x x^T) and [N,81,81] x [N,81,M], any K and M,
  *    with constant scalar Mul / Div nodes and one activation behind it folded

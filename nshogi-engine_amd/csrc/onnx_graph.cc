@@ -122,12 +122,14 @@ void Planner::lower(const Node& N, size_t K) {
             fail(N, "input '" + I + "' is " + dimsStr(Vals.at(I).dims) + " behind an Expand to " + dimsStr(Vals.at(I).expandTo) +
                         ": the Expand is a view that only Add, Sub, Mul, Div, Max and Min read, broadcasting it themselves (DESIGN.md section 13.3)");
     if (Op == "Shape" || !AnyRuntime) return hostFold(N);
+    // (Mod is in the op set for the host's shape chains alone)
+    if (Op == "Mod") fail(N, "op 'Mod' is outside the supported op set (DESIGN.md section 13)");
     const Val& X = get(N, 0);
     double PowOne = 0;
     // a line tensor is read by the ops of planner_lines.cc only
     for (const std::string& I : N.In)
         if (!I.empty() && Vals.at(I).runtime && Vals.at(I).form == kFormLine) return lineOp(N, K);
-    if (formView(N) || attentionOp(N) || normOp(N, K)) return;
+    if (seqView(N) || formView(N) || attentionOp(N) || normOp(N, K) || lateResidual(N)) return;
     if (bmmOperands(N)) return bmm(N, K);
     if (mixEntry(N)) return tokenMix(N, K);
     // [N,C,81] and the 4-D tensors exist only inside the patterns the calls above follow
@@ -144,8 +146,12 @@ void Planner::lower(const Node& N, size_t K) {
         }
         if (I.runtime && I.form == kFormScoreBias)
             fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " is a run-time attention bias: only the Add into the scores of the attention pattern reads it (DESIGN.md section 13.3)");
+        if (I.runtime && (I.form == kFormSeqTok || I.form == kFormSeqRows)) {
+            if ((Op == "MatMul" || Op == "Gemm") && J == 0 && has(N, 1) && !get(N, 1).runtime) return linear(N, K);
+            fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " holds the token rows seq-first: only a Linear (MatMul or Gemm with a constant weight), the Reshapes of nn.MultiheadAttention's export and Transpose [1,0,2] read it (DESIGN.md section 13.3)");
+        }
         if (I.runtime && I.form >= kFormChan3)
-            fail(N, "input '" + N.In[J] + "' " + dimsStr(I.dims) + " is consumed outside the token-view and attention patterns (DESIGN.md section 13.3)");
+            fail(N, "input '" + N.In[J] + "' " + I.shownStr() + " is consumed outside the token-view and attention patterns (DESIGN.md section 13.3)");
     }
     if (Op == "Softmax") {
         fail(N, "Softmax on " + dimsStr(X.dims) + ": only the softmax over the keys of the attention pattern, on [N,H,81,81] scores, is supported");

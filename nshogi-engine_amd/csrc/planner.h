@@ -21,13 +21,19 @@ using namespace nsg::onnx::wire;
 constexpr int64_t kBatch = INT64_MIN / 2; // the symbolic batch dimension inside folded shape values
 constexpr int kPending = -3; // the view of an open elementwise group: its buffer is assigned when the group is emitted
 
+// The batch times a constant inside folded shape values: N*H and N*81 of the stock transformer modules' export
+// (DESIGN.md section 13.3).  batchTimes(1) is kBatch itself; batchFactor is 0 for a plain number.
+constexpr int64_t kMaxBatchFactor = 1 << 24;
+inline int64_t batchTimes(int64_t K) { return kBatch + (K - 1); }
+inline int64_t batchFactor(int64_t V) { return V >= kBatch && V < kBatch + kMaxBatchFactor ? V - kBatch + 1 : 0; }
+
 inline int roundUp(int a, int b) { return (a + b - 1) / b * b; }
 
 inline std::string dimsStr(const std::vector<int64_t>& D) {
     std::string S = "[";
     for (size_t I = 0; I < D.size(); ++I) {
         if (I) S += ",";
-        S += D[I] == kBatch ? std::string("N") : std::to_string(D[I]);
+        S += D[I] == kBatch ? std::string("N") : batchFactor(D[I]) ? "N*" + std::to_string(batchFactor(D[I])) : std::to_string(D[I]);
     }
     return S + "]";
 }
@@ -52,13 +58,19 @@ enum Form {
     kFormHeadRows, // [N,H,K]: rows of (board, head), a view of a flat [N,H*K]; read by a MatMul with a constant [K,M] only
     kFormScoreBias, // [N,H,81,81] or [N,1,81,81]: a flat or head-row tensor as the run-time bias of attention scores
     kFormLine,      // [N,C,9,1] rank lines, [N,C,1,9] file lines, [N,C,18,1]: rows of (board, line); read by the ops of planner_lines.cc only
+    // the seq-first forms of nn.MultiheadAttention's export (seqView, planner_views.cc): the token rows under other names
+    kFormSeqTok,    // [81,N,C]: the token tensor under Transpose [1,0,2]
+    kFormSeqRows,   // [N*81,C]: those rows as a 2-D matrix, between a Reshape and the Linear that reads it
+    kFormSeqPacked, // the packed q / k / v projection on its way to three views: [81,N,3,E], [1,81,N,3,E], [3,81,N,1,E], [3,81,N,E]
+    kFormSeqHeads,  // [81,N*H,d]: q, k or v split into heads; dims hold [81,N,H,d] (Val::bh)
+    kFormSeqOut,    // probs x v on the way back: [81,N,H,d] (Val::bh: [81,N*H,d]); dims hold [81,N,H,d]
 };
 inline bool isAttForm(int F) { return F >= kFormTok4 && F <= kFormTokOut4; }
 
 // A tensor of the graph: a host value (constant or folded shape), or a runtime tensor on the device.
 struct Val {
     bool runtime = false;
-    std::vector<int64_t> dims; // runtime: logical ONNX dims, dims[0] = kBatch
+    std::vector<int64_t> dims; // runtime: logical ONNX dims, dims[0] = kBatch (the kFormSeq* forms: 81 or N*81 first)
     // host
     bool isInt = false;
     std::vector<double> f;
@@ -77,6 +89,11 @@ struct Val {
     View rtBias;
     int rtHead = 0;
     double rtScale = 1.0;
+    // kFormHeads .. kFormHeadOut and kFormSeqOut: the tensor is the 3-D form on the (board x head) axis, [N*H,81,d] for
+    // [N,H,81,d]; dims hold the 4-D shape, shownDims() the tensor's own
+    bool bh = false;
+    bool viaSeq = false;        // the attention pattern was entered through the seq-first head split
+    bool packedPart = false;    // kFormSeqTok: q, k or v taken out of the packed projection
     int headRows = 0;           // kFormHeadRows: H; v.stride is the stride of one (board, head) row, v.C = K
     std::vector<int64_t> expandTo; // a one-channel tensor behind an Expand: the shape the Expand names; dims stay the one-channel shape
     int lineLaunch = -1;        // kFormLine: the kLaunchLinePool that wrote it and has no other reader yet (-1: none)
@@ -89,6 +106,13 @@ struct Val {
     std::string producer;       // node name
     size_t count() const { return isInt ? i.size() : f.size(); }
     double at(size_t k) const { return isInt ? (double)i[k] : f[k]; }
+    // the tensor's own dims: dims, but for the 3-D forms on the (board x head) axis
+    std::vector<int64_t> shownDims() const {
+        if (!runtime || !bh || dims.size() != 4) return dims;
+        if (form == kFormSeqOut || form == kFormSeqHeads) return {dims[0], batchTimes(dims[2]), dims[3]};
+        return {batchTimes(dims[1]), dims[2], dims[3]};
+    }
+    std::string shownStr() const { return dimsStr(shownDims()); }
 };
 
 // An elementwise chain being fused into one launch.
@@ -171,6 +195,9 @@ class Planner {
     std::vector<int> VirtAlsoFlat;   // see assignBuffers
     struct PendingLaunch { Launch L; std::string out; Val V; };
     std::map<size_t, PendingLaunch> PendingMix; // a token-mixing launch waiting for its pattern's last node (planner_mix.cc)
+    // a seq-first Linear without residual or activation whose result is still read by one chain of views: tensor ->
+    // launch.  The Add of a token residual behind those views joins the launch (lateResidual, planner_views.cc)
+    std::map<std::string, size_t> OpenLinear;
 
     [[noreturn]] void fail(const Node& N, const std::string& Why) const {
         throw Error("node '" + N.Name + "' (" + N.Op + "): " + Why);
@@ -349,7 +376,15 @@ class Planner {
     std::vector<int64_t> reshapeTarget(const Node& N, const std::vector<int64_t>& SD);
     bool formView(const Node& N);   // Transpose, and Reshape / Flatten to or from the forms above
     Val headsSource(const Node& N, const Val& X0);
-    void attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND);
+    void attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND, int OutForm = kFormToken);
+    bool seqReaders(const std::string& T) const;
+    bool seqView(const Node& N);     // the seq-first forms of the stock transformer modules' export
+    bool lateResidual(const Node& N); // x + (views of a seq-first Linear): the Add joins the Linear's launch
+    int dataUses(const std::string& T) const { // live consumers that read the tensor's data (a Shape node does not)
+        auto U = Uses.find(T);
+        auto S = ShapeUses.find(T);
+        return (U == Uses.end() ? 0 : U->second) - (S == ShapeUses.end() ? 0 : S->second);
+    }
     bool flatFormView(const Node& N, const Val& X0); // token -> flat, flat -> head rows, flat / head rows -> score bias
     void headRowsDense(const Node& N, size_t Index); // MatMul of head rows [N,H,K] with a constant [K,M]
     bool bmmOperands(const Node& N) const;           // a MatMul of two run-time tensors outside the other patterns

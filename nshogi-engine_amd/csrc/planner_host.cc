@@ -38,7 +38,10 @@ const std::set<std::string>& opSet() {
         "PRelu", "Max", "Min", "Abs", "Neg", "InstanceNormalization", "Exp", "Log", "Sqrt", "Reciprocal", "Pow",
         "ReduceMin", "ReduceSum", "Expand",
         // Shape and Cast are folded on the host only (shape chains); a Gather of a runtime tensor is planner_gather.cc's
-        "Shape", "Gather", "Cast"};
+        "Shape", "Gather", "Cast",
+        // Mod is folded on host constants only (the shape checks of torch's unflatten); on a run-time tensor it is refused
+        // in the words of an op outside the set (lower, onnx_graph.cc)
+        "Mod"};
     return S;
 }
 
@@ -131,7 +134,7 @@ void Planner::hostFold(const Node& N) {
     auto Out = [&]() -> Val& { return Vals[N.Out[0]]; };
     if (Op == "Shape") {
         const Val& X = get(N, 0);
-        std::vector<int64_t> D = X.dims;
+        std::vector<int64_t> D = X.shownDims();
         if (X.runtime && X.flatOfSpatial) D = {kBatch, (int64_t)X.v.C * 81};
         int64_t S = N.attrI("start", 0), E = N.attrI("end", (int64_t)D.size());
         if (S < 0) S += (int64_t)D.size();
@@ -154,7 +157,7 @@ void Planner::hostFold(const Node& N) {
             for (size_t K = 0; K < X.count(); ++K) R.i.push_back(X.isInt ? X.i[K] : (int64_t)X.f[K]);
         } else if (To == 1 || To == 11) {
             for (size_t K = 0; K < X.count(); ++K) {
-                if (X.isInt && X.i[K] == kBatch) fail(N, "cannot cast the batch dimension to a float");
+                if (X.isInt && batchFactor(X.i[K])) fail(N, "cannot cast the batch dimension to a float");
                 R.f.push_back(X.at(K));
             }
         } else {
@@ -271,8 +274,14 @@ Val Planner::foldArithmetic(const Node& N, const Val& X) {
             if (R.isInt) {
                 const int64_t P1 = X.i[A], P2 = Y.i[B];
                 int64_t V;
-                const bool Sym = P1 == kBatch || P2 == kBatch;
-                if (Sym) {
+                const int64_t F1 = batchFactor(P1), F2 = batchFactor(P2);
+                const bool Sym = F1 || F2;
+                if (Sym && Op == "Mul" && !(F1 && F2) && (F1 ? P2 : P1) >= 1 && (F1 + F2) * (F1 ? P2 : P1) < kMaxBatchFactor) {
+                    V = batchTimes((F1 + F2) * (F1 ? P2 : P1)); // the batch times a constant: N*H, N*81 (planner.h)
+                } else if (Sym && (F1 > 1 || F2 > 1)) {
+                    fail(N, "arithmetic on a multiple of the symbolic batch dimension (" + dimsStr({P1}) + " " + Op + " " + dimsStr({P2}) +
+                                "): only a product with a positive constant is followed");
+                } else if (Sym) {
                     const int64_t Other = P1 == kBatch ? P2 : P1;
                     const bool Neutral = ((Op == "Mul") && Other == 1) || ((Op == "Div") && P1 == kBatch && Other == 1) ||
                                          ((Op == "Add" || Op == "Sub") && Other == 0 && !(Op == "Sub" && P2 == kBatch));
@@ -287,10 +296,25 @@ Val Planner::foldArithmetic(const Node& N, const Val& X) {
                 }
                 R.i.push_back(V);
             } else {
-                if ((X.isInt && X.i[A] == kBatch) || (Y.isInt && Y.i[B] == kBatch)) fail(N, "arithmetic on the symbolic batch dimension");
+                if ((X.isInt && batchFactor(X.i[A])) || (Y.isInt && batchFactor(Y.i[B]))) fail(N, "arithmetic on the symbolic batch dimension");
                 const double P1 = X.at(A), P2 = Y.at(B);
                 R.f.push_back(Op == "Add" ? P1 + P2 : Op == "Sub" ? P1 - P2 : Op == "Mul" ? P1 * P2 : P1 / P2);
             }
+        }
+        return R;
+    }
+    if (Op == "Mod") { // integers only, fmod = 0: the sign follows the divisor (torch's `dim % rank` in unflatten)
+        const Val& Y = host(N, 1, "the divisor");
+        if (!X.isInt || !Y.isInt || N.attrI("fmod", 0) != 0) fail(N, "Mod is folded on integer constants with fmod = 0 only");
+        if (Y.count() != 1 && Y.count() != X.count()) fail(N, "constant folding supports equal shapes or a scalar divisor");
+        R.isInt = true;
+        R.dims = X.dims;
+        for (size_t K = 0; K < X.count(); ++K) {
+            const int64_t A = X.i[K], B = Y.i[Y.count() == 1 ? 0 : K];
+            if (batchFactor(A) || batchFactor(B)) fail(N, "arithmetic on the symbolic batch dimension");
+            if (B == 0) fail(N, "integer division by zero");
+            const int64_t M = A % B;
+            R.i.push_back(M != 0 && (M < 0) != (B < 0) ? M + B : M);
         }
         return R;
     }
@@ -299,7 +323,7 @@ Val Planner::foldArithmetic(const Node& N, const Val& X) {
         if (Y && Y->count() != 1 && Y->count() != X.count()) fail(N, "constant folding supports equal shapes or a scalar exponent");
         R.dims = X.dims;
         for (size_t K = 0; K < X.count(); ++K) {
-            if (X.isInt && X.i[K] == kBatch) fail(N, "arithmetic on the symbolic batch dimension");
+            if (X.isInt && batchFactor(X.i[K])) fail(N, "arithmetic on the symbolic batch dimension");
             const double A = X.at(K);
             R.f.push_back(Y ? std::pow(A, Y->at(Y->count() == 1 ? 0 : K)) : Op == "Sqrt" ? std::sqrt(A) : Op == "Exp" ? std::exp(A) : Op == "Log" ? std::log(A) : 1.0 / A);
         }

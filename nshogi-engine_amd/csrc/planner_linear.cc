@@ -241,14 +241,21 @@ void Planner::linear(const Node& N, size_t Index) {
     const Val& X = get(N, 0);
     if (!X.runtime) fail(N, "the data input is a constant");
     const bool Dense = N.Op != "Conv";
-    const bool Tok = X.form == kFormToken; // a Linear over tokens: the 1x1 form of the conv, rows = (board, square)
-    if (Tok && N.Op != "MatMul") fail(N, "a token tensor " + dimsStr(X.dims) + " feeds MatMul, not " + N.Op);
-    LinearW Lw = Dense ? denseWeights(N, X, Tok) : convWeights(N, X);
+    // the token rows seq-first, [81,N,C] or the 2-D [N*81,C] (seqView): the same Linear over the same rows; the epilogue
+    // folds in those shapes, a token residual behind the views back joins later (lateResidual)
+    const bool Seq3 = X.form == kFormSeqTok, Seq2 = X.form == kFormSeqRows;
+    const bool Tok = X.form == kFormToken || Seq3 || Seq2; // a Linear over tokens: the 1x1 form of the conv, rows = (board, square)
+    if (Tok && N.Op != "MatMul" && !Seq2) fail(N, "a token tensor " + dimsStr(X.dims) + " feeds MatMul, not " + N.Op);
+    Val XTok = X; // (denseWeights reads a token tensor's channels off [N,81,C])
+    if (Seq3 || Seq2) XTok.dims = {kBatch, 81, (int64_t)X.v.C};
+    LinearW Lw = Dense ? denseWeights(N, XTok, Tok) : convWeights(N, X);
     const int Cout = Lw.Cout;
-    const std::vector<int64_t> Dims = Tok ? std::vector<int64_t>{kBatch, 81, Cout}
-                                          : Dense ? std::vector<int64_t>{kBatch, Cout} : std::vector<int64_t>{kBatch, Cout, 9, 9};
-    const int OutForm = Tok ? kFormToken : kFormPlain;
-    const Epilogue E = foldEpilogue(N, Index, Dims, Tok ? 2 : 1, OutForm, &Lw);
+    const std::vector<int64_t> Dims = Seq3 ? std::vector<int64_t>{81, kBatch, Cout}
+                                      : Seq2 ? std::vector<int64_t>{batchTimes(81), Cout}
+                                      : Tok  ? std::vector<int64_t>{kBatch, 81, Cout}
+                                             : Dense ? std::vector<int64_t>{kBatch, Cout} : std::vector<int64_t>{kBatch, Cout, 9, 9};
+    const int OutForm = Tok ? X.form : kFormPlain;
+    const Epilogue E = foldEpilogue(N, Index, Dims, Tok && !Seq2 ? 2 : 1, OutForm, &Lw);
     Launch L;
     L.name = E.name;
     ConvArgs& A = L.args.emplace<ConvArgs>();
@@ -277,7 +284,15 @@ void Planner::linear(const Node& N, size_t Index) {
     }
     L.out = freshView(Cout, !A.dense);
     P.flopsPerPosition += 2.0 * (A.dense ? 1 : 81) * A.taps * (double)Lw.CinW * Cout;
-    Val V = runtimeVal(N, Dims, OutForm);
+    Val V;
+    if (Seq3 || Seq2) {
+        V.runtime = true;
+        V.dims = Dims;
+        V.form = OutForm;
+        if (E.res.empty() && E.act == kActNone) OpenLinear[E.out] = P.launches.size();
+    } else {
+        V = runtimeVal(N, Dims, OutForm);
+    }
     V.v = L.out;
     V.producer = N.Name;
     emit(L);

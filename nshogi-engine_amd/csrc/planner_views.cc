@@ -36,6 +36,24 @@ std::vector<int64_t> Planner::reshapeTarget(const Node& N, const std::vector<int
     return ND;
 }
 
+// [N,C,81] tensor T is read by Transposes alone, [0,2,1] to tokens or [2,0,1] to the seq-first tokens, and by one of the
+// latter at least: what the exporter writes for tokens that go into a stock transformer module
+bool Planner::seqReaders(const std::string& T) const {
+    if (Outputs.count(T)) return false;
+    bool Seq = false;
+    for (size_t K = 0; K < Nodes.size(); ++K) {
+        if (Skip[K] || Nodes[K].Op == "Shape") continue;
+        for (const std::string& I : Nodes[K].In) {
+            if (I != T) continue;
+            const std::vector<int64_t> Perm = Nodes[K].attrInts("perm", {});
+            const bool S = Perm == std::vector<int64_t>{2, 0, 1};
+            if (Nodes[K].Op != "Transpose" || !(S || Perm == std::vector<int64_t>{0, 2, 1})) return false;
+            Seq = Seq || S;
+        }
+    }
+    return Seq;
+}
+
 // ---- views between [N,C,9,9], [N,C,81], tokens [N,81,C] and the attention pattern's 4-D shapes: no launch, except
 // the Reshape that closes the attention pattern.  Returns false when N is not such a view (the caller goes on).
 bool Planner::formView(const Node& N) {
@@ -78,7 +96,8 @@ bool Planner::formView(const Node& N) {
         }
         if (F == kFormGroup3) fail(N, "Transpose of " + dimsStr(X0.dims) + ": the groups [N,G,M] of a GroupNorm pattern feed an InstanceNormalization only");
         if (F == kFormPlain) return false; // refused by the caller, with the shapes
-        if (F >= kFormChan3) interior(N, 0);
+        // ([N,C,81] read seq-first as well, by Transpose [2,0,1]: both Transposes are views of the same rows, seqView)
+        if (F >= kFormChan3 && !(F == kFormChan3 && seqReaders(N.In[0]))) interior(N, 0);
         const Val X = F == kFormToken ? ready(N.In[0]) : X0;
         const std::vector<int64_t>& D = X.dims;
         if ((F == kFormToken || F == kFormChan3) && Perm == std::vector<int64_t>{0, 2, 1}) {
@@ -275,7 +294,8 @@ Val Planner::headsSource(const Node& N, const Val& X0) {
 }
 
 // The Reshape of [N,81,H,d] to ND = [N,81,H*d] that closes the attention pattern: its one launch
-void Planner::attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND) {
+// (OutForm: kFormToken, or the seq-first form the closing Reshape of nn.MultiheadAttention's export names, X0 then [81,N,H,d])
+void Planner::attentionLaunch(const Node& N, const Val& X0, const std::vector<int64_t>& ND, int OutForm) {
     const int64_t H = X0.dims[2], Hd = X0.dims[3];
     Launch L;
     L.name = X0.chain + "+" + N.Name;
@@ -299,7 +319,15 @@ void Planner::attentionLaunch(const Node& N, const Val& X0, const std::vector<in
     }
     L.out = freshView((int)(H * Hd), true);
     P.flopsPerPosition += 2.0 * (2.0 * 81 * 81 * (double)Hd) * (double)H; // q k^T and probs x v
-    Val V = runtimeVal(N, ND, kFormToken);
+    Val V;
+    if (OutForm == kFormToken) {
+        V = runtimeVal(N, ND, kFormToken);
+    } else {
+        V.runtime = true;
+        V.dims = ND;
+        V.form = OutForm;
+        V.producer = N.Name;
+    }
     V.v = L.out;
     emit(L);
     Vals[N.Out[0]] = V;
@@ -324,14 +352,17 @@ bool Planner::attentionOp(const Node& N) {
         return true;
     };
     if (Op == "Softmax") {
-        if (FA != kFormScores) fail(N, "Softmax on " + dimsStr(A.dims) + ": only the softmax over the keys of [N,H,81,81] attention scores is supported");
+        if (FA != kFormScores) fail(N, "Softmax on " + A.shownStr() + ": only the softmax over the keys of [N,H,81,81] attention scores is supported");
         int64_t Axis = N.attrI("axis", -1);
-        if (Axis < 0) Axis += 4;
+        if (Axis < 0) Axis += A.bh ? 3 : 4;
+        if (A.bh) ++Axis; // the 3-D scores [N*H,81,81]
         if (Axis != 3) fail(N, "Softmax over axis " + std::to_string(N.attrI("axis", -1)) + " of the attention scores: the keys (axis -1) only");
         interior(N, 0);
         return put(A, kFormProbs, A.dims);
     }
     if (Op == "MatMul") {
+        if (isAttForm(FA) && isAttForm(FB) && A.bh != B->bh)
+            fail(N, "MatMul of " + A.shownStr() + " and " + B->shownStr() + ": one operand is on the (board x head) axis, the other is not");
         if (FA == kFormHeads && FB == kFormHeadsT) {
             interior(N, 0);
             interior(N, 1);
@@ -357,12 +388,15 @@ bool Planner::attentionOp(const Node& N) {
             V.chain = A.chain + "+" + B->chain;
             return put(V, kFormHeadOut, {kBatch, A.dims[1], 81, B->dims[3]});
         }
-        fail(N, "MatMul of " + dimsStr(A.dims) + " and " + dimsStr(B->dims) + " is outside the attention pattern (q k^T, then softmax x v; DESIGN.md section 13.3)");
+        fail(N, "MatMul of " + A.shownStr() + " and " + B->shownStr() + " is outside the attention pattern (q k^T, then softmax x v; DESIGN.md section 13.3)");
     }
     // Mul / Div / Add with a constant
     const bool AR = isAttForm(FA);
     const Val& T = AR ? A : *B;
     const Val& Cst = AR ? *B : A;
+    if (Op == "Add" && T.viaSeq)
+        fail(N, "an Add on the attention scores " + T.shownStr() + " of nn.MultiheadAttention's export form: attn_mask, key_padding_mask and is_causal are outside "
+                "the stock-module pattern (a mask of -inf entries is no constant bias of the attention launch; DESIGN.md section 13.3)");
     if (Cst.runtime) {
         // one bias computed at run time, a view of a flat or head-row tensor, added to the scores
         if (Op != "Add" || T.form != kFormScores)
@@ -613,6 +647,175 @@ void Planner::split(const Node& N) {
         V.dims[(size_t)ChanAxis] = Sizes[J];
         Vals[N.Out[J]] = V;
     }
+}
+
+// ---- the seq-first forms: what the exporter writes for nn.MultiheadAttention, and so for nn.TransformerEncoderLayer
+// and nn.TransformerEncoder ("stock transformer modules").  The module works on [81,N,E]; every
+// tensor below is a view of the board-major token rows and costs no launch:
+//   [N,C,81] -Transpose [2,0,1]-> [81,N,C] <-Transpose [1,0,2]-> tokens [N,81,C];  [81,N,C] <-Reshape-> [N*81,C]
+//   a Linear (MatMul (+ Add) or Gemm) on [81,N,C] or [N*81,C] is the token Linear (linear, planner_linear.cc)
+//   the packed projection [81,N,3E] -Reshape-> [81,N,3,E] -Unsqueeze 0-> [1,81,N,3,E] -Transpose [3,1,2,0,4]->
+//     [3,81,N,1,E] -Squeeze 3-> [3,81,N,E] -Gather k, axis 0-> [81,N,E]: the view at channel k E of the QKV rows
+//   [81,N,E] -Reshape-> [81,N*H,d] -Transpose [1,0,2]-> [N*H,81,d]: q, k and v on the (board x head) axis; k^T by
+//     Transpose [1,2,0] of [81,N*H,d] or [0,2,1] of [N*H,81,d].  [N*H,81,d] -Reshape-> [N,H,81,d] joins the 4-D forms;
+//     without it MatMul, Mul and Softmax work on the 3-D forms (attentionOp, Val::bh)
+//   probs x v: [N,H,81,d] -Transpose [2,0,1,3]-> [81,N,H,d], or [N*H,81,d] -Transpose [1,0,2]-> [81,N*H,d]; the
+//     Reshape to [N*81,E] (or [81,N,E]) closes the pattern: the one kLaunchAttention
+// Returns false when N reads none of these forms and enters none (the caller goes on).
+bool Planner::seqView(const Node& N) {
+    using Dv = std::vector<int64_t>;
+    const std::string& Op = N.Op;
+    if (N.In.empty() || N.In[0].empty()) return false;
+    auto It = Vals.find(N.In[0]);
+    if (It == Vals.end() || !It->second.runtime) return false;
+    const Val X0 = It->second;
+    const int F = X0.form;
+    const bool SeqForm = F >= kFormSeqTok && F <= kFormSeqOut;
+    const bool Transpose = Op == "Transpose", Reshape = Op == "Reshape";
+    const Dv Perm = Transpose ? N.attrInts("perm", {}) : Dv();
+    const bool Enter = Transpose && ((F == kFormChan3 && Perm == Dv{2, 0, 1}) || (F == kFormToken && Perm == Dv{1, 0, 2}) ||
+                                     (F == kFormHeadOut && !X0.bh && Perm == Dv{2, 0, 1, 3}));
+    if (!SeqForm && !X0.bh && !Enter) return false;
+    const bool PackedOp = F == kFormSeqPacked && (Op == "Unsqueeze" || Op == "Squeeze" || Op == "Gather");
+    if (!Transpose && !Reshape && !PackedOp) return false; // a Linear, the attention pattern's arithmetic, or refused by the caller
+    const std::string Shown = X0.shownStr();
+    auto put = [&](Val V, int Form, Dv Dims, bool Chain) {
+        V.form = Form;
+        V.dims = std::move(Dims);
+        V.producer = N.Name;
+        if (Chain) V.chain += (V.chain.empty() ? "" : "+") + N.Name;
+        else V.chain.clear();
+        Vals[N.Out[0]] = V;
+        return true;
+    };
+    // the views on the way back from a Linear keep it open for the residual Add behind them (lateResidual)
+    auto passLinear = [&]() {
+        auto Open = OpenLinear.find(N.In[0]);
+        if (Open == OpenLinear.end()) return;
+        if (dataUses(N.In[0]) == 1 && !Outputs.count(N.In[0])) OpenLinear[N.Out[0]] = Open->second;
+        OpenLinear.erase(N.In[0]);
+    };
+    const Dv& D = X0.dims;
+    if (Transpose) {
+        if (F == kFormChan3) { // (the [0,2,1] Transpose beside this one is formView's)
+            if (!seqReaders(N.In[0])) interior(N, 0);
+            return put(X0, kFormSeqTok, {81, kBatch, D[1]}, false);
+        }
+        if (F == kFormToken) return put(ready(N.In[0]), kFormSeqTok, {81, kBatch, D[2]}, false);
+        if (F == kFormSeqTok && Perm == Dv{1, 0, 2}) {
+            passLinear();
+            return put(X0, kFormToken, {kBatch, 81, D[2]}, false);
+        }
+        if (F != kFormSeqTok && F != kFormSeqRows && F != kFormSeqPacked) interior(N, 0);
+        if (F == kFormSeqHeads && Perm == Dv{1, 0, 2}) return put(X0, kFormHeads, {kBatch, D[2], 81, D[3]}, true);
+        if (F == kFormSeqHeads && Perm == Dv{1, 2, 0}) return put(X0, kFormHeadsT, {kBatch, D[2], D[3], 81}, true);
+        if (F == kFormHeads && X0.bh && Perm == Dv{0, 2, 1}) return put(X0, kFormHeadsT, {kBatch, D[1], D[3], 81}, true);
+        if (F == kFormHeadOut && Perm == (X0.bh ? Dv{1, 0, 2} : Dv{2, 0, 1, 3})) return put(X0, kFormSeqOut, {81, kBatch, D[1], D[3]}, true);
+        if (F == kFormSeqPacked && D.size() == 5 && D[0] == 1 && Perm == Dv{3, 1, 2, 0, 4}) return put(X0, kFormSeqPacked, {D[3], D[1], D[2], 1, D[4]}, false);
+        fail(N, "Transpose of " + Shown + " with perm " + dimsStr(Perm) + " is outside the seq-first forms of nn.MultiheadAttention's export (DESIGN.md section 13.3)");
+    }
+    if (PackedOp) {
+        if (Op == "Unsqueeze" && D.size() == 4 && D[0] == 81 && axes(N, 4, true) == Dv{0}) return put(X0, kFormSeqPacked, {1, D[0], D[1], D[2], D[3]}, false);
+        if (Op == "Squeeze" && D.size() == 5 && D[0] == 3 && D[3] == 1 && axes(N, 5) == Dv{3}) return put(X0, kFormSeqPacked, {D[0], D[1], D[2], D[4]}, false);
+        if (Op == "Gather" && D.size() == 4 && D[0] == 3 && N.attrI("axis", 0) == 0) {
+            const Val& Iv = host(N, 1, "Gather's indices");
+            if (Iv.dims.empty() && Iv.count() == 1 && Iv.isInt && Iv.i[0] >= -3 && Iv.i[0] < 3) {
+                const int64_t Part = (Iv.i[0] + 3) % 3;
+                Val V = X0;
+                V.v.offset += (int)(Part * D[3]);
+                V.v.C = (int)D[3];
+                V.packedPart = true;
+                return put(V, kFormSeqTok, {81, kBatch, D[3]}, false);
+            }
+        }
+        fail(N, Op + " of the packed q / k / v projection " + Shown + " is outside the split nn.MultiheadAttention's export writes: Reshape to [81,N,3,E], Unsqueeze 0, "
+                    "Transpose [3,1,2,0,4], Squeeze 3, Gather of part 0, 1 or 2 along axis 0 (DESIGN.md section 13.3)");
+    }
+    // Reshape: the exporter writes every target of these forms in full
+    const Dv Sh = ints(N, 1, "the target shape");
+    for (int64_t S : Sh)
+        if (S == 0 || S == -1) fail(N, "Reshape of " + Shown + " to " + dimsStr(Sh) + ": the target shapes of the seq-first forms are taken only when written in full");
+    if (F == kFormSeqTok) {
+        const int64_t C = D[2];
+        if (Sh == Dv{batchTimes(81), C}) return put(X0, kFormSeqRows, Sh, false);
+        // one head: the exporter drops the product N*1, and the head split of a part of the packed projection is the
+        // Reshape to its own shape [81,N,E]
+        const bool Split1 = Sh == D && X0.packedPart;
+        if (Sh == D && !Split1) {
+            passLinear();
+            return put(X0, kFormSeqTok, D, false);
+        }
+        if (Sh.size() == 4 && Sh[0] == 81 && Sh[1] == kBatch && Sh[2] == 3 && Sh[3] * 3 == C) return put(X0, kFormSeqPacked, Sh, false);
+        const int64_t H = Sh.size() == 3 ? batchFactor(Sh[1]) : 0;
+        if (H < 1 || Sh[0] != 81 || Sh[2] <= 0 || H * Sh[2] != C)
+            fail(N, "the seq-first tokens " + Shown + " can become [N*81,C], the packed projection [81,N,3,E] or the head split [81,N*H,d], not " + dimsStr(Sh));
+        const int64_t Hd = Sh[2];
+        if (!X0.packedPart)
+            fail(N, "the head split " + dimsStr(Sh) + " of '" + N.In[0] + "', which is no part of a packed q / k / v projection: the stock-module pattern is self-attention "
+                        "with one in_proj_weight; separate projections (kdim or vdim other than embed_dim, cross-attention) are outside it (DESIGN.md section 13.3)");
+        if (Hd % 4 != 0 || Hd > kMaxHeadDim)
+            fail(N, "head dimension " + std::to_string(Hd) + ": the attention kernel takes multiples of 4 up to " + std::to_string(kMaxHeadDim));
+        if (X0.v.offset % 4 != 0) fail(N, "'" + N.In[0] + "' starts at channel " + std::to_string(X0.v.offset) + " of its row: the attention kernel reads views at multiples of 4");
+        Val V = X0;
+        V.scale = 1.0;
+        V.packedPart = false;
+        V.bh = V.viaSeq = true;
+        V.chain.clear();
+        return put(V, kFormSeqHeads, {81, kBatch, H, Hd}, true);
+    }
+    if (F == kFormSeqRows) {
+        if (Sh != Dv{81, kBatch, D[1]}) fail(N, "the token rows " + Shown + " can become [81,N," + std::to_string(D[1]) + "] again, not " + dimsStr(Sh));
+        passLinear();
+        return put(X0, kFormSeqTok, Sh, false);
+    }
+    interior(N, 0);
+    if (F == kFormHeads && X0.bh) {
+        if (Sh != D) fail(N, "q, k or v on the (board x head) axis " + Shown + " can become " + dimsStr(D) + ", not " + dimsStr(Sh));
+        Val V = X0;
+        V.bh = false;
+        return put(V, kFormHeads, D, true);
+    }
+    if (F == kFormSeqOut) { // the Reshape that closes the pattern: one launch
+        const int64_t E = D[2] * D[3];
+        const bool Rows = Sh == Dv{batchTimes(81), E};
+        if (!Rows && Sh != Dv{81, kBatch, E})
+            fail(N, "the attention output " + Shown + " is reshaped to " + dimsStr(Sh) + ", not to [N*81," + std::to_string(E) + "] or [81,N," + std::to_string(E) + "]");
+        attentionLaunch(N, X0, Sh, Rows ? kFormSeqRows : kFormSeqTok);
+        return true;
+    }
+    fail(N, "Reshape of " + Shown + " to " + dimsStr(Sh) + " is outside the seq-first forms of nn.MultiheadAttention's export (DESIGN.md section 13.3)");
+}
+
+// ---- x + (a seq-first Linear seen through its views back to tokens): the exporter's Shape nodes stand between the
+// Linear and its residual Add, so the epilogue could not look ahead; the Add joins the launch here, as the residual the
+// hand-written form's Linear takes.  Only while the Linear has no residual and no activation, its result has this one
+// reader, and the residual was written before the Linear's launch.
+bool Planner::lateResidual(const Node& N) {
+    if (N.Op != "Add" || N.In.size() != 2 || N.In[0] == N.In[1]) return false;
+    for (size_t Side = 0; Side < 2; ++Side) {
+        const std::string& T = N.In[Side];
+        const std::string& Other = N.In[1 - Side];
+        auto Open = OpenLinear.find(T);
+        if (Open == OpenLinear.end() || !Vals.count(Other)) continue;
+        const Val& A = Vals.at(T);
+        const Val& O = Vals.at(Other);
+        if (A.form != kFormToken || !O.runtime || O.form != kFormToken || O.dims != A.dims || O.group >= 0 || !O.expandTo.empty()) continue;
+        if (dataUses(T) != 1 || Outputs.count(T)) continue;
+        const size_t At = Open->second;
+        ConvArgs& C = std::get<ConvArgs>(P.launches[At].args);
+        if (C.res.buf != kNoRes || C.act != kActNone) continue;
+        bool Before = O.v.buf == -1; // the graph input
+        for (size_t K = 0; K < At; ++K) Before = Before || P.launches[K].out.buf == O.v.buf;
+        if (!Before) continue;
+        C.res = O.v;
+        P.launches[At].name += "+" + N.Name;
+        Val V = A;
+        V.producer = N.Name;
+        OpenLinear.erase(Open);
+        Vals[N.Out[0]] = V;
+        return true;
+    }
+    return false;
 }
 
 } // namespace nsg::graph
