@@ -143,6 +143,12 @@ int nsg_set_precision(nsg_evaluator* ev, int precision);
  *    A Gather of an activation with constant indices (o[:, 0], tok[:, 40],
  *    x[:, IDX], logits[:, MAP]) and a Slice with step -1 over a whole board
  *    axis (x.flip(2), x.flip(3)) are one launch each.
+ *    Over the channels of a spatial, token or flat tensor, with the axis kept
+ *    (keepdim=True), the L1 and L2 norms (x.norm, torch.linalg.vector_norm),
+ *    the sum of squares and torch.logsumexp are one launch each beside max,
+ *    min and sum, and F.normalize(x, p = 1 or 2, dim = channels, eps > 0) is
+ *    one fused launch; a softmax over the channels is x - logsumexp(x) and Exp.
+ *    The L2 norm is not rescaled: x * x overflows as in fp32.
  *    A general graph always runs in
  *    exact fp32, whatever nsg_set_precision asked for.
  * When both refuse, the load fails with NSG_E_FORMAT and a message giving both

@@ -140,6 +140,10 @@ struct Exec {
     hipError_t operator()(const ChanReduceArgs& A) const {
         return launchGraphChanReduce(dv(A.in), A.redMode, A.scale, ptr(out), out.stride, rowsOf(out), s);
     }
+
+    hipError_t operator()(const NormalizeArgs& A) const {
+        return launchGraphNormalize(dv(A.in), A.p, A.eps, ptr(out), out.stride, rowsOf(out), s);
+    }
 };
 
 } // namespace

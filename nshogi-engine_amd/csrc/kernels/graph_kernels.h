@@ -1,6 +1,6 @@
 // graph_kernels.h -- launch interface of the general graph path's kernels (graph_conv.hip, graph_pool.hip,
 // graph_ops.hip, graph_attention.hip, graph_norm.hip, graph_bmm.hip, graph_linepool.hip, graph_gconv.hip, graph_tokenmix.hip,
-// graph_gather.hip, graph_chanreduce.hip).  Their one caller for a plan's launches is ../graph_exec.hip, which marshals
+// graph_gather.hip, graph_chanreduce.hip, graph_normalize.hip).  Their one caller for a plan's launches is ../graph_exec.hip, which marshals
 // each argument record of onnx_graph.h (ConvArgs, EltProgram, ...) into the call below that runs it; nsg_capi.hip calls
 // launchGraphOutputs only.
 //
@@ -180,7 +180,17 @@ hipError_t launchGraphGather(const float* src, long blockFloats, const int* rowT
 // may start at any channel of its rows (the ragged ends of an offset that is no multiple of 4 are read with scalar
 // loads); nothing outside [offset, offset + C) is read.  in.stride a multiple of 4, in.p 16-byte aligned.  The order of a
 // sum depends on (C, offset) only.  Max and min are fmaxf / fminf folds from -inf / +inf: a NaN element is skipped.
+// kRedL1: the sum of fabsf(x); kRedSumSq: the sum of x * x as an fmaf chain; kRedL2: sqrtf of that, no rescaling (x * x
+// overflows where it does in f32); kRedLogSumExp: m + logf(sum expf(x - m)) with m the row's max in a first pass, m
+// itself where m is +inf or -inf (a row of -inf gives -inf).  The same lanes, fold order and butterfly for every mode.
 hipError_t launchGraphChanReduce(DevView in, int mode, float scale, float* out, int outStride, long rows, hipStream_t stream);
+
+// The L1 (p = 1) or L2 (p = 2) normalisation over the in.C channels of each of `rows` rows (graph_normalize.hip):
+// out[row][c] = x[c] / fmaxf(n, eps) with n the row's norm exactly as launchGraphChanReduce's kRedL1 / kRedL2 computes
+// it, eps > 0, the division correctly rounded; out[row][in.C .. outStride-1] = 0.  `in` may start at any channel of its
+// rows and nothing outside [offset, offset + C) is read; in.stride and outStride multiples of 4, outStride >= in.C,
+// in.p and out 16-byte aligned.  `out` must not overlap the rows of `in`: a row is read twice.
+hipError_t launchGraphNormalize(DevView in, int p, float eps, float* out, int outStride, long rows, hipStream_t stream);
 
 // [B*81][C] spatial view -> [B][outStride] flat in ONNX order (index c * 81 + square)
 hipError_t launchGraphFlatten(DevView in, float* out, int outStride, int boards, hipStream_t stream);

@@ -105,6 +105,8 @@ void Planner::lower(const Node& N, size_t K) {
     const std::string& Op = N.Op;
     if (N.Out.empty()) fail(N, "no output");
     if (PendingMix.count(K)) return mixFlush(K); // the last node of a token-mixing pattern: its launch goes here
+    // the Div of an F.normalize chain: its launch goes here, or (a chain that does not fit after all) its held-back nodes do
+    if (OpenNormalize.count(K) && normalizeClose(N, K)) return;
     if (Op == "Constant") {
         if (!Vals.count(N.Out[0])) fail(N, "unsupported Constant attribute (value tensor or value_float only)");
         return;
@@ -171,7 +173,8 @@ void Planner::lower(const Node& N, size_t K) {
         pool(N);
     } else if (Op == "Split") {
         split(N);
-    } else if (Op == "ReduceMin" || Op == "ReduceSum" || (Op == "ReduceMax" && channelAxis(N, X)) ||
+    } else if (Op == "ReduceMin" || Op == "ReduceSum" || Op == "ReduceL1" || Op == "ReduceL2" || Op == "ReduceSumSquare" ||
+               Op == "ReduceLogSumExp" || (Op == "ReduceMax" && channelAxis(N, X)) ||
                (Op == "ReduceMean" && channelAxis(N, X) > 1)) { // (a ReduceMean over the channels of a spatial tensor: refused below, as before)
         reduceChannels(N);
     } else if (Op == "GlobalAveragePool" || Op == "ReduceMean" || Op == "GlobalMaxPool" || Op == "ReduceMax") {

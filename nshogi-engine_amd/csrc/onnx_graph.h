@@ -104,12 +104,13 @@ struct EltSrc {
 enum LaunchKind {
     kLaunchConv = 0, kLaunchElt, kLaunchMean, kLaunchConcat, kLaunchFlatten, kLaunchLayerNorm, kLaunchAttention,
     kLaunchPool, kLaunchMax, kLaunchGroupNorm, kLaunchRmsNorm, kLaunchBmm, kLaunchLinePool, kLaunchTokenMix, kLaunchGather,
-    kLaunchChanReduce
+    kLaunchChanReduce, kLaunchNormalize
 };
 // PoolArgs: the max, or the mean over kh x kw taps with the zero halo counted (count_include_pad = 1) or left out
 enum PoolMode { kPoolMax = 0, kPoolAvgInclude, kPoolAvgExclude };
-// ChanReduceArgs: what is taken over the channels of a row
-enum RedMode { kRedMax = 0, kRedMin, kRedSum };
+// ChanReduceArgs: what is taken over the channels of a row.  kRedL1 = sum |x|, kRedSumSq = sum x^2, kRedL2 = its square
+// root, kRedLogSumExp = log sum exp(x) through the row's max.  plan_dump prints the values (redMode=%d): they do not change.
+enum RedMode { kRedMax = 0, kRedMin, kRedSum, kRedL1, kRedSumSq, kRedL2, kRedLogSumExp };
 constexpr int kMaxHeadDim = 64; // channels per attention head (a multiple of 4)
 struct CopySeg { View v; int dstOff = 0; };
 
@@ -318,10 +319,10 @@ struct GatherArgs {
     template <class Fn> void views(Fn F) { F("in", in); }
 };
 
-// kLaunchChanReduce: the max, min or sum (redMode) over the in.C channels of every row of `in` (spatial or token rows,
-// or flat rows; a view at any channel offset) -> out, a one-channel tensor of the same rows: channel 0 holds the
-// result, channels 1..15 zeros.  A sum is multiplied by `scale` after its last add: 1 for ReduceSum, the f32 constant
-// 1/C for a ReduceMean.
+// kLaunchChanReduce: the max, min, sum, L1 norm, sum of squares, L2 norm or log-sum-exp (redMode) over the in.C channels
+// of every row of `in` (spatial or token rows, or flat rows; a view at any channel offset) -> out, a one-channel tensor
+// of the same rows: channel 0 holds the result, channels 1..15 zeros.  A sum is multiplied by `scale` after its last
+// add: 1 for ReduceSum, the f32 constant 1/C for a ReduceMean.
 struct ChanReduceArgs {
     View in;
     int redMode = kRedMax;
@@ -330,9 +331,20 @@ struct ChanReduceArgs {
     template <class Fn> void views(Fn F) { F("in", in); }
 };
 
+// kLaunchNormalize: F.normalize over the channels, x / max(norm_p(x), eps) on every row of `in` (spatial or token rows,
+// or flat rows; a view at any channel offset) -> out, a tensor of in.C channels of the same rows.  p: 1 or 2; eps > 0.
+// The norm has the bits of kLaunchChanReduce's kRedL1 / kRedL2.  `out` is never `in`'s buffer: a row is read twice.
+struct NormalizeArgs {
+    View in;
+    int p = 2;
+    float eps = 0.f;
+    static constexpr int kind() { return kLaunchNormalize; }
+    template <class Fn> void views(Fn F) { F("in", in); }
+};
+
 using LaunchArgs = std::variant<ConvArgs, EltProgram, SquareReduceArgs, ConcatSegs, FlattenArgs, LayerNormArgs, AttentionArgs,
                                 PoolArgs, GroupNormArgs, RmsNormArgs, BmmArgs, LinePoolArgs, TokenMixArgs, GatherArgs,
-                                ChanReduceArgs>;
+                                ChanReduceArgs, NormalizeArgs>;
 
 struct Launch {
     std::string name; // the ONNX node(s) it runs

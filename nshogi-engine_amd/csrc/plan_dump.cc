@@ -70,6 +70,7 @@ void columns(Columns& C, const BmmArgs& A) { C.in = A.in; C.res = noResidual(); 
 void columns(Columns& C, const TokenMixArgs& A) { C.in = A.in; C.res = noResidual(); C.wOff = A.wOff; C.act = A.act; }
 void columns(Columns& C, const GatherArgs& A) { C.in = A.in; C.res = noResidual(); }
 void columns(Columns& C, const ChanReduceArgs& A) { C.in = A.in; C.scale = A.scale; }
+void columns(Columns& C, const NormalizeArgs& A) { C.in = A.in; C.eps = A.eps; }
 template <class T> void columns(Columns& C, const T& A) { C.in = A.in; } // the records that hold `in` alone
 
 // the fields behind the columns, per record, where they are not the defaults
@@ -94,6 +95,7 @@ void tail(const Launch& L, const GatherArgs& A) { // the width is out's stride; 
     std::printf(" gatherRows=%d gatherBlock=%ld gatherWidth=%d gatherTabOff=%zu", A.gatherRows, A.gatherBlock, L.out.stride, A.gatherTabOff);
 }
 void tail(const Launch&, const ChanReduceArgs& A) { std::printf(" redMode=%d", A.redMode); } // the mean's factor is the column `scale`
+void tail(const Launch&, const NormalizeArgs& A) { std::printf(" normP=%d", A.p); } // eps is a column
 template <class T> void tail(const Launch&, const T&) {}
 
 // the offsets into `weights` a record reads its constants at

@@ -198,6 +198,10 @@ class Planner {
     // a seq-first Linear without residual or activation whose result is still read by one chain of views: tensor ->
     // launch.  The Add of a token residual behind those views joins the launch (lateResidual, planner_views.cc)
     std::map<std::string, size_t> OpenLinear;
+    // an F.normalize chain waiting for its Div (planner_norms.cc): the Div's index -> the ReduceL1 / ReduceL2 at `reduce`,
+    // the Clip and the optional Expand between them (`interior`, marked in Skip), none of them lowered yet
+    struct PendingNormalize { size_t reduce = 0; std::vector<size_t> interior; int p = 2; float eps = 0.f; };
+    std::map<size_t, PendingNormalize> OpenNormalize;
 
     [[noreturn]] void fail(const Node& N, const std::string& Why) const {
         throw Error("node '" + N.Name + "' (" + N.Op + "): " + Why);
@@ -362,6 +366,8 @@ class Planner {
     bool decomposedNorm(const Node& N, size_t Index);
     const Node* follow(const std::string& T, size_t After, const Node& From);
     bool lastAxis(const Node& N, const Val& X);
+    bool normalizeOpen(const Node& N, size_t Index);  // a ReduceL1 / ReduceL2 that starts an F.normalize chain: deferred to its Div
+    bool normalizeClose(const Node& N, size_t Index); // that Div: one kLaunchNormalize, or the chain's nodes lowered one by one
     // planner_pool.cc
     void pool(const Node& N);
     void reduceSquares(const Node& N);

@@ -36,7 +36,7 @@ const std::set<std::string>& opSet() {
         "Concat", "Slice", "Identity", "Constant", "Transpose", "LayerNormalization", "Erf", "Softmax",
         "MaxPool", "AveragePool", "GlobalMaxPool", "ReduceMax", "Split", "Clip", "HardSwish", "HardSigmoid", "LeakyRelu",
         "PRelu", "Max", "Min", "Abs", "Neg", "InstanceNormalization", "Exp", "Log", "Sqrt", "Reciprocal", "Pow",
-        "ReduceMin", "ReduceSum", "Expand",
+        "ReduceMin", "ReduceSum", "Expand", "ReduceL1", "ReduceL2", "ReduceSumSquare", "ReduceLogSumExp",
         // Shape and Cast are folded on the host only (shape chains); a Gather of a runtime tensor is planner_gather.cc's
         "Shape", "Gather", "Cast",
         // Mod is folded on host constants only (the shape checks of torch's unflatten); on a run-time tensor it is refused

@@ -219,8 +219,80 @@ bool Planner::decomposedNorm(const Node& N, size_t Index) {
     return true;
 }
 
+// ---- F.normalize over the channels, as the exporter writes it:
+//   n = ReduceL2(x) or ReduceL1(x) over the channel axis, keepdims 1;  c = Clip(n, min = eps);  [e = Expand(c, Shape(x))];
+//   y = Div(x, e or c)
+// with a constant scalar eps > 0, no max bound, the same x as the Div's numerator, and n, c, e read by the chain only (x
+// may have other readers).  Matched forward from the reduction on the graph's structure; the nodes are held back (the
+// Clip and the Expand in Skip) until the Div, where the Expand's target, folded by then, is checked against x's shape:
+// one kLaunchNormalize.  A chain that starts like this and deviates is no error: normalizeOpen returns false and every
+// node is lowered as it stands, a kLaunchChanReduce and elementwise nodes.
+bool Planner::normalizeOpen(const Node& N, size_t Index) {
+    const Val& X = get(N, 0);
+    if (!channelAxis(N, X) || N.attrI("keepdims", 1) == 0 || !absorbable(N.Out[0])) return false;
+    const Node* Cl = onlyConsumer(N.Out[0], Index);
+    double Eps = 0;
+    if (!Cl || Cl->Op != "Clip" || Cl->In.size() < 2 || Cl->In[0] != N.Out[0] || Cl->In[1].empty() || Cl->In[1] == N.Out[0] ||
+        (Cl->In.size() > 2 && !Cl->In[2].empty()) || !scalarAhead(Cl->In[1], &Eps) || !((float)Eps > 0.f) || !absorbable(Cl->Out[0]))
+        return false;
+    PendingNormalize Pn;
+    Pn.reduce = Index;
+    Pn.interior = {indexOf(Cl)};
+    Pn.p = N.Op == "ReduceL1" ? 1 : 2;
+    Pn.eps = (float)Eps;
+    const Node* Dv = onlyConsumer(Cl->Out[0], indexOf(Cl));
+    if (Dv && Dv->Op == "Expand" && Dv->In.size() == 2 && Dv->In[0] == Cl->Out[0] && Dv->In[1] != Cl->Out[0] && absorbable(Dv->Out[0])) {
+        Pn.interior.push_back(indexOf(Dv));
+        Dv = onlyConsumer(Dv->Out[0], indexOf(Dv));
+    }
+    if (!Dv || Dv->Op != "Div" || Dv->In.size() != 2 || Dv->In[0] != N.In[0] || Dv->In[1] != Nodes[Pn.interior.back()].Out[0]) return false;
+    for (size_t K : Pn.interior) Skip[K] = true;
+    OpenNormalize[indexOf(Dv)] = Pn;
+    return true;
+}
+
+bool Planner::normalizeClose(const Node& N, size_t Index) {
+    const PendingNormalize Pn = OpenNormalize.at(Index);
+    OpenNormalize.erase(Index);
+    const Node& Rd = Nodes[Pn.reduce];
+    const Val& X = get(Rd, 0);
+    const int Kind = channelAxis(Rd, X);
+    // the Expand is the view expandView would make of it: its target is the shape x has
+    bool Fits = Kind != 0;
+    if (Fits && Pn.interior.size() == 2) {
+        const Node& Ex = Nodes[Pn.interior[1]];
+        auto It = Vals.find(Ex.In[1]);
+        std::vector<int64_t> One = X.dims, T;
+        One[Kind == 2 ? 2 : 1] = 1;
+        Fits = It != Vals.end() && !It->second.runtime && It->second.isInt && broadcast(One, It->second.i, &T) && T == X.dims;
+    }
+    if (!Fits) { // the chain's nodes one by one, here: nothing else reads what they compute
+        reduceChannels(Rd);
+        for (size_t K : Pn.interior) {
+            Skip[K] = false;
+            lower(Nodes[K], K);
+        }
+        return false;
+    }
+    Launch L;
+    L.name = Rd.Name;
+    for (size_t K : Pn.interior) L.name += "+" + Nodes[K].Name;
+    L.name += "+" + N.Name;
+    const int C = Kind == 2 ? (int)X.dims[2] : (int)X.dims[1];
+    const std::vector<int64_t> Dims = X.dims;
+    const int Form = X.form;
+    L.args = NormalizeArgs{ready(Rd.In[0]).v, Pn.p, Pn.eps}; // a view at any channel offset
+    L.out = freshView(C, Kind != 3);
+    Val V = runtimeVal(N, Dims, Form);
+    V.v = L.out;
+    emit(L);
+    Vals[N.Out[0]] = V;
+    return true;
+}
+
 // ---- the normalisations beyond BatchNorm and the single LayerNormalization node.  Returns false when N is none.
 bool Planner::normOp(const Node& N, size_t Index) {
+    if (N.Op == "ReduceL1" || N.Op == "ReduceL2") return normalizeOpen(N, Index);
     if (N.Op == "LayerNormalization" && get(N, 0).runtime && get(N, 0).form == kFormChanLast) {
         layerNorm(N);
         return true;

@@ -104,7 +104,8 @@ void Planner::reduceSquares(const Node& N) {
     Vals[N.Out[0]] = V;
 }
 
-// ---- ReduceMax / ReduceMin / ReduceSum (and ReduceMean on token and flat rows) over the channels: one kLaunchChanReduce
+// ---- ReduceMax / ReduceMin / ReduceSum / ReduceL1 / ReduceL2 / ReduceSumSquare / ReduceLogSumExp (and ReduceMean on token
+// and flat rows) over the channels: one kLaunchChanReduce
 // Which kind of tensor X is when the node's axes are exactly its channel axis: 1 spatial (axis 1 of [N,C,9,9]), 2 token
 // (axis 2 of [N,81,C]), 3 flat (axis 1 of [N,C] / [N,C,1,1]); 0 otherwise.
 int Planner::channelAxis(const Node& N, const Val& X) {
@@ -135,7 +136,8 @@ void Planner::reduceChannels(const Node& N) {
     Launch L;
     L.name = N.Name;
     ChanReduceArgs& A = L.args.emplace<ChanReduceArgs>();
-    A.redMode = Op == "ReduceMax" ? kRedMax : Op == "ReduceMin" ? kRedMin : kRedSum;
+    A.redMode = Op == "ReduceMax" ? kRedMax : Op == "ReduceMin" ? kRedMin : Op == "ReduceL1" ? kRedL1 : Op == "ReduceL2" ? kRedL2
+                : Op == "ReduceSumSquare" ? kRedSumSq : Op == "ReduceLogSumExp" ? kRedLogSumExp : kRedSum;
     A.scale = Op == "ReduceMean" ? (float)(1.0 / C) : 1.f; // the mean: the sum times the f32 constant 1/C, applied after the last add
     A.in = ready(N.In[0]).v; // a view at any channel offset: the kernel reads the ragged ends with scalar loads
     L.out = freshView(1, Kind != 3);
