@@ -331,9 +331,11 @@ int nsg_get_stats(nsg_evaluator* ev, uint64_t* batches, uint64_t* positions);
  * launch; *fallbacks: launches that gave up and were re-run. */
 int nsg_get_team_stats(nsg_evaluator* ev, int* enabled, int* members_last, uint64_t* fallbacks);
 /* How the most recent forward pass launched its trunk: 0 = per-layer kernels (or the persistent launch whose workgroups
- * own whole boards: no hand-off), 1 = the team trunk, 2 = the cooperative trunk -- the two-way K split of 65 ... CUs/2
- * boards of a 256-channel F16M6 net as ONE launch whose two workgroups per board hand their channel halves to each
- * other (same residency rule, device token, give-up and re-run as the team trunk; NSG_COOP_TRUNK=0 switches it off).
+ * own whole boards: no hand-off), 1 = the team trunk, 2 = the cooperative trunk -- a K-split plan of an F16M6 net as
+ * ONE launch whose workgroups per board hand their output slices to each other: from 17 boards up to CUs/2 of a
+ * 256-channel net (the four-way K split with its row groups, then the two-way K split), up to CUs/3 of a 192-channel
+ * net (the three-way K split), wherever the launch fits the chip at once (tests/golden/launch_forms.txt has the exact
+ * ranges; same residency rule, device token, give-up and re-run as the team trunk; NSG_COOP_TRUNK=0 switches it off).
  * *coop_enabled: 1 in use, 0 off (not applicable, switched off, or after a fallback), -1 another process holds the
  * device's token. */
 int nsg_get_last_launch_kind(nsg_evaluator* ev, int* kind, int* coop_enabled);
@@ -365,6 +367,13 @@ int nsg_get_last_slab_split(nsg_evaluator* ev, int* slab_split);
  * the first pass).  An F16M8 evaluator runs small batches for which it has no F16M8 tile plan
  * (channel counts other than 256) as F16X3. */
 int nsg_get_last_trunk_precision(nsg_evaluator* ev, int* precision);
+/* The launch form a forward pass of `batch` boards would take NOW, in the fields the nsg_get_last_* family reports
+ * after one: kind and whole_trunk / parts (nsg_get_last_launch_kind, _form), the plan and its chains
+ * (nsg_get_last_plan), the splits (nsg_get_last_split, _slab_split) and the trunk's arithmetic.  Launches nothing.  Any
+ * pointer may be null. */
+int nsg_get_launch_form(nsg_evaluator* ev, int batch, int* kind, int* whole_trunk, int* parts, int* boards_per_group,
+                        int* fragments_per_wave, int* waves_per_group, int* chains, int* row_split, int* k_split,
+                        int* slab_split, int* trunk_precision);
 
 /* ---- the general graph path ---- */
 #define NSG_GRAPH_AUTO 0    /* ONNX: the specialised path when it accepts the model, else the general path */

@@ -128,6 +128,7 @@ def load_library():
     lib.nsg_get_last_trunk_precision.argtypes = [vp, ip]
     lib.nsg_get_last_split.argtypes = [vp, ip, ip]
     lib.nsg_get_last_slab_split.argtypes = [vp, ip]
+    lib.nsg_get_launch_form.argtypes = [vp, i] + [ip] * 11
     lib.nsg_compute_gather_blocking.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp]
     lib.nsg_compute_gather_nonblocking.argtypes = [vp, vp, sz, vp, vp, i, vp, vp, vp]
     lib.nsg_set_graph_mode.argtypes = [vp, i]
@@ -138,6 +139,10 @@ def load_library():
     lib.nsg_cpu_executor_compute.argtypes = [vp, vp, sz, vp, vp, vp]
     _lib = lib
     return lib
+
+
+def _trunk_precision_name(value):
+    return {v: k for k, v in _PREC_NAMES.items() if k not in ("f32", "f16")}.get(value, value)
 
 
 def _check(rc):
@@ -368,6 +373,16 @@ class Evaluator:
         _check(self._lib.nsg_get_last_launch_form(self._h, ctypes.byref(wt), ctypes.byref(parts)))
         return {"whole_trunk": wt.value, "parts": parts.value}
 
+    def launch_form(self, batch):
+        """nsg_get_launch_form: what a forward of `batch` boards would report NOW, without launching it:
+        (last_launch_kind()[0], last_launch_form(), last_plan())."""
+        v = [ctypes.c_int() for _ in range(11)]
+        _check(self._lib.nsg_get_launch_form(self._h, int(batch), *[ctypes.byref(x) for x in v]))
+        kind, wt, parts, nb, nfrag, nwaves, chains, rs, ks, ss, tp = (x.value for x in v)
+        plan = {"boards_per_group": nb, "fragments_per_wave": nfrag, "waves_per_group": nwaves, "chains": chains,
+                "row_split": rs, "k_split": ks, "slab_split": ss, "trunk_precision": _trunk_precision_name(tp)}
+        return {0: "per_layer", 1: "team", 2: "coop"}.get(kind, kind), {"whole_trunk": wt, "parts": parts}, plan
+
     def last_plan(self):
         """Launch plan of the most recent forward pass (nsg_get_last_plan)."""
         v = [ctypes.c_int() for _ in range(4)]
@@ -382,7 +397,7 @@ class Evaluator:
         d["slab_split"] = ss.value
         tp = ctypes.c_int()
         _check(self._lib.nsg_get_last_trunk_precision(self._h, ctypes.byref(tp)))
-        d["trunk_precision"] = {v: k for k, v in _PREC_NAMES.items() if k not in ("f32", "f16")}.get(tp.value, tp.value)
+        d["trunk_precision"] = _trunk_precision_name(tp.value)
         return d
 
 

@@ -9,6 +9,8 @@
 #ifndef NSG_KERNELS_H
 #define NSG_KERNELS_H
 
+#include "../launch_form.h" // Precision, ConvPlan, ConvTuning and the host-only launch decision
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -37,9 +39,7 @@ namespace nsg {
 //              [24 B: e2m3(lo), channel order 0..31][1 B E8M0][3 B 0][1 B E8M0 again][3 B 0]
 // (the exponent sits in both trailing dwords of a block: the conv's main loop reads the codes as 16 + 8 bytes and the
 // exponent as the block's last dword, mfma_tile.h kSplitRead)
-enum Precision { kFp32 = 0, kFp16 = 1, kBf16 = 2, kF16x3 = 3, kF16m8 = 4, kF16m6 = 5 };
-// the two split-precision trunk formats that run their correction terms on the MX instruction
-constexpr bool isMx(int prec) { return prec == kF16m8 || prec == kF16m6; }
+// (enum Precision, isMx, headPrecision: launch_form.h)
 constexpr int kM8LoShift = 12;   // stored lo byte = e4m3(lo * 2^12)
 constexpr int kM8WLoShift = 10;  // weight record  = e4m3(w_lo * 2^10)
 constexpr int kM8WHiShift = -2;  // weight record  = e4m3(w_hi * 2^-2); both products carry 2^-10
@@ -47,8 +47,6 @@ constexpr int kM8ScaleByte = 127 - 10; // E8M0 block scale of the weight operand
 
 // Bytes one activation channel occupies (a kF16x3 pair is 2 + 2 bytes, kF16m8 2 + 1 + 1).
 inline int elemSize(int prec) { return (prec == kFp32 || prec == kF16x3 || isMx(prec)) ? 4 : 2; }
-// Precision of the 1x1 heads / value MLP of an evaluator whose trunk runs at `prec`.
-inline int headPrecision(int prec) { return isMx(prec) ? (int)kF16x3 : prec; }
 // Channels per 128-byte K chunk of the trunk convolution.
 inline int chunkChannels(int prec) { return 128 / elemSize(prec); }
 // MFMA K-slabs per (chunk, tap): two halves of the chunk, or for kF16x3 the three
@@ -78,31 +76,8 @@ hipError_t launchExtractBitsAct(void* dst, const uint64_t* src, int batch,
                                 hipStream_t stream);
 
 // ---- MFMA tile kernels (mfma_tile.h) ----
-struct ConvPlan {
-    int nb;      // boards per workgroup
-    int nfrag;   // 16-channel output fragments per wave (fixed at pack time)
-    int nwaves;  // waves per workgroup
-    int msplit = 1; // wave groups that split the tile's row fragments between them (small one-board tiles: 2)
-    int ksplit = 1; // kF16m8 one-board tiles: waves of a channel group that split the input-channel chunk pairs between them
-    int sslab = 1;  // MX two-board tiles at mid batches: waves of a channel group that split every chunk pair's slabs between them
-};
-constexpr int kNfrag = 4; // every packed tensor uses 4 fragments (64 channels) per wave
-
-// Tuning overrides (0 = automatic), read from NSG_CONV_NB / _NWAVES / _NFRAG when an
-// evaluator is created.
-struct ConvTuning {
-    int nb = 0, nwaves = 0, nfrag = 0, msplit = 0; // msplit: NSG_CONV_MSPLIT (1 = never split rows)
-    int splitBatch = 1;    // NSG_SPLIT_BATCH=0: never run a batch as a full part + remainder
-    int splitBatchMax3 = 9;  // NSG_SPLIT_BATCH_MAX: largest batch, in quarters of the CU count, that starts with a full chip of two-board tiles
-    int rowsplit8Max = -1; // NSG_ROWSPLIT8_MAX_BATCH: largest batch whose four-way K split also splits the rows over two workgroups (-1: CUs / 8)
-    int ksplit3 = 1;       // NSG_KSPLIT3=0: 192-channel nets keep the plans they had before the three-way K split
-    int slabSplit = 0;     // NSG_SLAB_SPLIT=1: slab-split two-board tiles at mid batches (measured 8-11 % slower than the plans they would replace: opt-in)
-    bool fullTilesOnly = false; // kF16m8: 4 fragments per wave at every batch size
-};
+// (ConvPlan, ConvTuning, chooseConvPlan: launch_form.h)
 ConvTuning readConvTuning();
-
-// Picks a tile configuration for (batch, cout).
-ConvPlan chooseConvPlan(int batch, int cout, int computeUnits, const ConvTuning& tune = ConvTuning());
 
 // 3x3 convolution + folded-BN bias (+ residual) (+ ReLU) on
 // activations [boards][81][cin] -> [boards][81][cout].  Buffers must hold
@@ -117,25 +92,23 @@ hipError_t launchConv3x3(const void* x, const void* wfrag, const float* bias,
 // Persistent trunk: every 3x3 layer (stem + 2 per block) in ONE launch.  A layer
 // list is built once with trunkLayersBytes()/fillTrunkLayer() on the host, uploaded,
 // and reused for every batch size.  Needs cout == nwaves*64 (one workgroup covers all
-// output channels of its boards); canRunTrunk() says whether a plan qualifies.
+// output channels of its boards); canRunTrunk() (launch_form.h) says whether a plan qualifies.
 size_t trunkLayerBytes();
 size_t trunkLayerStampsOffset(); // (diagnostic builds) byte offset of a layer's stamp pointer inside its list entry
 void fillTrunkLayer(void* hostLayers, int index, const void* x, const void* wfrag,
                     const float* bias, const void* residual, void* y, int cin,
                     int cout, int relu, float accScale, bool outF16x3 = false);
-bool canRunTrunk(int cout, const ConvPlan& plan);
 hipError_t launchTrunk(const void* devLayers, int nLayers, int batch, int prec,
                        const ConvPlan& plan, hipStream_t stream);
 
 // Cooperative trunk (mfma_tile.h, coopTrunkKernel): every 3x3 layer of a mid batch whose boards are shared by several
 // workgroups (K-split plans) in ONE launch; workgroups of a board hand their output slices to each other through
-// agent-scope stores / loads and one flag per (board, member) in `flags` (batch x members unsigned, zeroed before the
-// launch).  kF16m6: 256 channels, the two-way K split (65 ... CUs/2 boards) and the four-way K split with its row
-// groups (17 ... CUs/4); 192 channels, the three-way K split (17 ... CUs/3).  All batch x members workgroups must be
-// resident at once.  `status`: host-mapped int raised when a bounded spin runs out.
-bool canRunCoopTrunk(int cout, int stemKdim, int prec, const ConvPlan& plan, bool* firstSeparate = nullptr);
-bool coopFits(int boards, int members, int computeUnits); // every workgroup of the launch resident at once (per XCD)
-int coopMembers(int cout, const ConvPlan& plan); // workgroups per board
+// agent-scope stores / loads and one flag per (board, member) in `flags` (batch x members unsigned; a launch's flag
+// values count up from `flagBase`, so the array is cleared only when the 24-bit values run out).  kF16m6: 256 channels,
+// the two-way K split (CUs/4 + 1 ... CUs/2 boards) and the four-way K split with its row groups (17 ... CUs/4); 192
+// channels, the three-way K split (17 ... CUs/3).  All batch x members workgroups must be resident at once
+// (canRunCoopTrunk, coopMembers, coopFits: launch_form.h).  `status`: host-mapped int raised when a bounded spin runs out.
+bool coopSameXcd(); // tile::kCoopSameXcd, for LaunchConfig
 // (faultBoard >= 0: test hook -- that board's second member leaves at once, so its first waits in vain)
 hipError_t launchCoopTrunk(const void* devLayers, int nLayers, int batch, int cout, int prec, const ConvPlan& plan,
                            unsigned* flags, unsigned flagBase, int* status, hipStream_t stream, int faultBoard);
@@ -154,7 +127,6 @@ struct TeamLayer {
     int kdim, cout, relu;
     float accScale;
 };
-constexpr int kTeamMaxBoards = 16;
 // Hand-off buffers of a launch: `set` = four images of imageStride bytes (>= boards x 81 x 1024); layer l <
 // nLayers - 1 writes image l % 4 of boards 0 .. boards-1.  When the launch starts every byte of those boards is 0xff;
 // when it ends that holds again but for image (nLayers - 2) % 4.  `other` = the set the launch before this one used:
@@ -172,9 +144,6 @@ struct TeamHandoff {
     int bitChannels;
 };
 bool teamTrunkSupports(int channels, int stemKdim, int boards);
-// workgroups per board of a launch of `boards` boards of a `channels`-wide trunk on a device of `computeUnits` CUs
-// (every member must be resident at once); 0: no team size fits.  forceRowGroups > 0: at most that many row groups.
-int teamMembers(int boards, int channels, int computeUnits, int forceRowGroups);
 #ifdef TEAM_STAMPS
 void teamTrunkDumpStamps(); // diagnostic builds: per-phase cycles of one member, printed when an evaluator is destroyed
 #endif

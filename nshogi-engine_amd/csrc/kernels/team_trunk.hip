@@ -4,7 +4,7 @@
 // Why: at one board a 3x3 layer is 2.36 MB of weights against 15 MFLOP -- a weight-bandwidth problem.  The
 // per-layer tile kernels give a board to 24 workgroups that each stream 622 KB of records through ONE L1 for 108
 // MFMAs per wave, behind a launch boundary, a kernel-start latency and a tile round trip per layer: 14.5 us per
-// layer.  Here a board belongs to a TEAM of 96 / 48 / 32 / 16 workgroups (teamMembers() below; one per CU).  Member
+// layer.  Here a board belongs to a TEAM of 96 / 48 / 32 / 16 workgroups (teamMembers(), launch_form.h; one per CU).  Member
 // (j, h) computes 16 output channels (weight fragment j) of row group h -- 1, 2, 3 or all 6 of the board's 16-row
 // fragments: its eight waves split K by 32-channel chunk, so a wave's share of a layer's weights is 18 records =
 // 18 KiB = 72 registers, requested as soon as the layer before has stored its output.  Per layer a member loads
@@ -450,23 +450,6 @@ __global__ __launch_bounds__(kThreads, 2) void teamTrunkKernel(const TeamLayer* 
 }
 
 } // namespace
-
-// Members per board = weight fragments (trunk channels / 16: 16 or 12) x row groups, as many as fit the chip's CUs (a
-// member owns a CU: 147 KB of LDS): with 16 fragments on 256 CUs 96 (one row fragment each) for one or two boards,
-// 48 (two) for three to five, 32 (three) for six to eight, 16 (the whole board) for nine to sixteen.  Measured, evals/s
-// at 2 / 3 / 4 / 5 boards: 96 members 11.2k / - / - / -, 48 members 9.2k / 13.5k / 17.7k / 21.6k, 32 members 7.8k /
-// 11.5k / 15.4k / 18.8k; 6 / 8 boards: 32 members 22.5k / 29.3k, 16 members 16.2k / 21.3k
-// (profiles/r03/g_team_trunk_members.txt).  Every member must be resident at once (they wait for each other): a
-// device with fewer CUs (a partition, a CU mask) gets the largest team that fits, or none -- 0 -- and the caller
-// runs the per-layer kernels.  `forceRowGroups` (NSG_TEAM_MEMBERS / 16) asks for fewer row groups than that.
-int teamMembers(int boards, int channels, int computeUnits, int forceRowGroups) {
-    const int nj = channels / 16;
-    for (int rg : {6, 3, 2, 1}) {
-        if (forceRowGroups > 0 && rg > forceRowGroups) continue;
-        if ((long)boards * nj * rg <= computeUnits) return nj * rg;
-    }
-    return 0;
-}
 
 // 256 or 192 trunk channels: a member's eight waves take one 32-channel chunk of K each (a wave's share of a layer's
 // records is 72 registers), so at most eight chunks; rows of an image are 1024 bytes.

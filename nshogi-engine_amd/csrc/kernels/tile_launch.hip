@@ -23,66 +23,6 @@ ConvTuning readConvTuning() {
     return t;
 }
 
-ConvPlan chooseConvPlan(int batch, int cout, int computeUnits, const ConvTuning& tune) {
-    ConvPlan p;
-    const int groups = cout / (kNfrag * 16); // 64-channel weight groups
-    // Full tiles: 4 fragments (64 channels) per wave, widest workgroup that divides
-    // the channel groups (its waves share one LDS image of the input tile).
-    p.nfrag = kNfrag;
-    // A full tile's wave needs the whole register file of its SIMD, so a CU hosts
-    // 4 waves: one 4-wave workgroup or two 2-wave workgroups fill it, a 3-wave
-    // workgroup leaves a SIMD idle (40x384: 2-wave groups +17 % over 3-wave groups).
-    p.nwaves = (groups % 4 == 0) ? 4 : (groups % 2 == 0) ? 2 : (groups % 3 == 0) ? 3 : 1;
-    // Two boards per workgroup waste less of the last 16-row fragment (162 -> 176
-    // rows vs 81 -> 96) but halve the grid: use them once the grid still covers
-    // most of the chip.
-    const int simds = computeUnits * 4;
-    auto waves = [&](int nb, int nfrag) { return ((batch + nb - 1) / nb) * (cout / (16 * nfrag)); };
-    p.nb = (waves(2, 4) * 4 >= simds * 3) ? 2 : 1;
-    // Small batches: a wave's run time is set by fragments-per-wave x K, so when
-    // the grid leaves SIMDs idle give each wave fewer channels (2 or 1 fragments,
-    // four waves per workgroup) until the chip is covered.
-    if (waves(p.nb, 4) * 4 < simds * 3) {
-        for (int nf : {2, 1}) {
-            for (int nb : {2, 1}) {
-                if (cout % (4 * nf * 16) != 0) continue;
-                if (waves(nb, nf) * 4 >= simds * 3 || (nf == 1 && nb == 1)) {
-                    p.nb = nb; p.nfrag = nf; p.nwaves = 4;
-                    goto chosen;
-                }
-            }
-        }
-    }
-chosen:
-    // A small-tile plan whose grid needs a second round of workgroups (more workgroups than CUs:
-    // the CUs that get two take twice as long as the rest) loses to one full one-board tile per
-    // board when those tiles fit in one round: B = 129..191 on 256 CUs (129: 2.13 -> 1.9 ms).
-    if (p.nfrag < 4 && tune.nfrag == 0 && tune.nb == 0) {
-        const int perBoard = cout / (16 * p.nfrag * 4); // workgroups per tile of the small plan
-        const int nwg = ((batch + p.nb - 1) / p.nb) * perBoard;
-        if (nwg > computeUnits && batch <= computeUnits && 2 * batch > computeUnits) {
-            p.nb = 1; p.nfrag = 4;
-            p.nwaves = (groups % 4 == 0) ? 4 : (groups % 2 == 0) ? 2 : (groups % 3 == 0) ? 3 : 1;
-        }
-    }
-    const int kEnvNb = tune.nb, kEnvNwaves = tune.nwaves, kEnvNfrag = tune.fullTilesOnly ? 4 : tune.nfrag;
-    if (kEnvNb == 1 || kEnvNb == 2) p.nb = kEnvNb;
-    if (kEnvNfrag) {
-        const int v = kEnvNfrag;
-        if (v == 1 || v == 2) { p.nfrag = v; p.nwaves = 4; }
-        if (v == 4) { p.nfrag = 4; p.nwaves = (groups % 4 == 0) ? 4 : (groups % 2 == 0) ? 2 : (groups % 3 == 0) ? 3 : 1; }
-    }
-    if (kEnvNwaves >= 1 && kEnvNwaves <= 4 && groups % kEnvNwaves == 0 && p.nfrag == kNfrag) p.nwaves = kEnvNwaves;
-    // One board, one fragment per wave: every wave reads every row fragment from LDS for one MFMA
-    // each (LDS-bound).  Two wave groups on half the rows each with two fragments per wave cover
-    // the same 64 channels per workgroup with half the LDS reads.
-    if (p.nb == 1 && p.nfrag == 1 && p.nwaves == 4 && tune.msplit != 1 && kEnvNfrag == 0) {
-        p.nfrag = 2;
-        p.msplit = 2;
-    }
-    return p;
-}
-
 hipError_t launchConv3x3(const void* x, const void* wfrag, const float* bias,
                          const void* residual, void* y, int batch, int cin,
                          int cout, int relu, float accScale, int prec,
@@ -134,11 +74,6 @@ void fillTrunkLayer(void* hostLayers, int index, const void* x, const void* wfra
     memcpy((unsigned char*)hostLayers + (size_t)index * sizeof(tile::Args), &a, sizeof(a));
 }
 
-bool canRunTrunk(int cout, const ConvPlan& plan) {
-    return plan.nfrag == kNfrag && plan.msplit == 1 && plan.ksplit == 1 && plan.sslab == 1 && cout == plan.nwaves * 64 &&
-           (plan.nwaves == 4 || plan.nwaves == 3);
-}
-
 hipError_t launchTrunk(const void* devLayers, int nLayers, int batch, int prec,
                        const ConvPlan& plan, hipStream_t stream) {
     if (batch <= 0 || nLayers <= 0) return hipErrorInvalidValue;
@@ -154,32 +89,7 @@ hipError_t launchTrunk(const void* devLayers, int nLayers, int batch, int prec,
     return hipErrorInvalidValue;
 }
 
-// The K-split plans of an f16m6 evaluator.  *firstSeparate: the stem has fewer chunk pairs than the plan splits K by and
-// runs another kernel (its own launch, ahead of the cooperative one, which then starts at the first residual layer).
-bool canRunCoopTrunk(int cout, int stemKdim, int prec, const ConvPlan& plan, bool* firstSeparate) {
-    if (prec != kF16m6 || plan.nb != 1 || plan.nfrag != kNfrag || plan.sslab != 1) return false;
-    const bool rows = plan.msplit == 1 || plan.msplit == 2 || plan.msplit == 3 || plan.msplit == 6;
-    bool sep = false, ok = false;
-    if (cout == 256 && plan.nwaves == 4 && plan.ksplit == 2 && plan.msplit == 1) { ok = true; sep = !(stemKdim % 128 == 0 && stemKdim <= 256); }
-    else if (cout == 256 && plan.nwaves == 4 && plan.ksplit == 4 && rows) { ok = true; sep = !(stemKdim == 256); }
-    else if (cout == 192 && plan.nwaves == 3 && plan.ksplit == 3 && rows) { ok = true; sep = !(stemKdim == 192); }
-    if (firstSeparate) *firstSeparate = sep;
-    return ok;
-}
-
-int coopMembers(int cout, const ConvPlan& plan) {
-    const bool rowWG = plan.msplit > 1 && plan.ksplit > 1;
-    const int chanGroups = plan.nwaves / (rowWG ? plan.ksplit : plan.msplit * plan.ksplit);
-    return cout / (chanGroups * plan.nfrag * 16) * (rowWG ? plan.msplit : 1);
-}
-
-// Every workgroup of the cooperative launch resident at once.  Same-XCD hand-off (tile::kCoopSameXcd): blockIdx.x picks
-// the XCD (workgroups are dealt round-robin, gridDim.x is padded to a multiple of eight), so the members of
-// ceil(boards / 8) boards must fit ONE XCD's share of the CUs.
-bool coopFits(int boards, int members, int computeUnits) {
-    if (tile::kCoopSameXcd) return (long)((boards + 7) / 8) * members <= computeUnits / 8;
-    return (long)boards * members <= computeUnits;
-}
+bool coopSameXcd() { return tile::kCoopSameXcd; }
 
 hipError_t launchCoopTrunk(const void* devLayers, int nLayers, int batch, int cout, int prec, const ConvPlan& plan,
                            unsigned* flags, unsigned flagBase, int* status, hipStream_t stream, int faultBoard) {

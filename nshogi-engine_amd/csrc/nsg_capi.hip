@@ -595,16 +595,56 @@ void teamDeviceUnlock(int gpu) {
     }
 }
 
-// Workgroups per board of a team launch of B boards on this evaluator's device; 0: the batch does not run as a team.
-int teamMembersFor(const nsg_evaluator* ev, int B) {
-    if (ev->teamLayerCount <= 0 || !ev->teamEnabled || B > ev->teamMaxBatch) return 0;
-    return nsg::teamMembers(B, ev->F, ev->prop.multiProcessorCount, ev->teamForceRowGroups);
+// Everything chooseLaunchForm (launch_form.h) reads of this evaluator, as plain values.
+nsg::LaunchConfig launchConfigOf(const nsg_evaluator* ev) {
+    // (NSG_KSPLIT4_MAX_BATCH: experiment knob, read once -- largest batch that takes the four-way K split)
+    static const int k4max = [] { const char* e = getenv("NSG_KSPLIT4_MAX_BATCH"); return e ? atoi(e) : -1; }();
+    nsg::LaunchConfig c;
+    c.prec = ev->prec;
+    c.F = ev->F; c.cpad = ev->cpad; c.blocks = ev->blocks;
+    c.trunkLayerCount = ev->trunkLayerCount;
+    c.cus = ev->prop.multiProcessorCount;
+    c.numChains = ev->numChains;
+    c.tuning = ev->tuning;
+    c.useTrunkKernel = ev->useTrunkKernel;
+    c.chainMinBatch = ev->chainMinBatch;
+    c.chainDelayUs = ev->chainDelayUs;
+    c.teamMaxBatch = ev->teamMaxBatch;
+    c.teamForceRowGroups = ev->teamForceRowGroups;
+    c.coopForced = ev->coopForced;
+    c.ksplit4Max = k4max;
+    c.coopSameXcd = nsg::coopSameXcd();
+    c.outsideM8Window = ev->W->outsideM8Window;
+    c.teamAvailable = ev->teamLayerCount > 0 && ev->teamEnabled;
+    c.coopAvailable = ev->coopEnabled && ev->teamStatusDev && ev->coopFlags.p;
+    return c;
 }
 
-// The whole forward of a batch of at most kTeamMaxBoards boards with the team trunk.
+// The value / policy heads of boards [off, off + count) behind a trunk whose output for them starts at `x` (the tail
+// of every forward).
+int enqueueHeads(nsg_evaluator* ev, void* x, int off, int count, int hprec, hipStream_t s) {
+    Range headsRange("nsg.heads");
+    float* policy = (float*)ev->policy.p + (size_t)off * NSG_MOVE_INDEX_MAX;
+    void* vfeat = (unsigned char*)ev->vfeat.p + (size_t)off * ev->fc1K * nsg::elemSize(hprec);
+    float* hidden = (float*)ev->hidden.p + (size_t)off * ev->vh;
+    NSG_HIP(nsg::launchHeads(x, ev->W->heads.w.p, (const float*)ev->W->heads.bias.p, policy, vfeat, count, ev->F,
+                             ev->headsCout, ev->vc, ev->fc1K, ev->W->heads.accScale, hprec, s));
+    const size_t partStride = (size_t)ev->batchMax * ev->vh; // floats between the K slices' partial sums
+    NSG_HIP(nsg::launchDense(vfeat, ev->W->fc1.w.p, (const float*)ev->W->fc1.bias.p, hidden, count, ev->fc1K,
+                             ev->vh, partStride, ev->W->fc1.accScale, hprec, s));
+    NSG_HIP(nsg::launchValueOut(hidden, (const float*)ev->W->fc1.bias.p, nsg::denseSplits(ev->fc1K, hprec), partStride,
+                                (const float*)ev->W->fc2W.p, (const float*)ev->W->fc2B.p,
+                                (float*)ev->value.p + off, (float*)ev->draw.p + off, count, ev->vh, s));
+    return NSG_OK;
+}
+
+// The output of the persistent launches' layer list: the buffer its rotation ends in.
+void* trunkListOutput(nsg_evaluator* ev) {
+    return ev->trunkOut = (ev->blocks % 2 == 1) ? ev->act[2].p : ev->act[0].p;
+}
+
+// The whole forward of a batch of at most kTeamMaxBoards boards with the team trunk (under the device's token).
 int enqueueTeam(nsg_evaluator* ev, int B, int members, hipStream_t s, hipEvent_t trunkBegin, hipEvent_t trunkEnd) {
-    const int prec = nsg::kF16x3;
-    ev->lastTrunkPrec = prec;
     {   // (the feature bitboards are decoded by the first layer of the team launch itself)
         Range r("nsg.trunk");
         if (trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
@@ -621,53 +661,24 @@ int enqueueTeam(nsg_evaluator* ev, int B, int members, hipStream_t s, hipEvent_t
         NSG_HIP(nsg::launchTeamTrunk((const nsg::TeamLayer*)ev->teamLayers.p, ev->teamLayerCount, B, ev->F, members, ho,
                                      ev->teamStatusDev, s, shortBy));
         ev->teamLastMembers = members;
-        NSG_HIP(hipEventRecord(ev->teamDone, s)); // (under the token's mutex: enqueueForward)
+        NSG_HIP(hipEventRecord(ev->teamDone, s)); // (under the token's mutex: enqueuePersistent)
         ev->teamDirty[1 - ev->teamSet] = 0;
         ev->teamDirty[ev->teamSet] = B;
         ev->teamSet = 1 - ev->teamSet;
         if (trunkEnd) NSG_HIP(hipEventRecord(trunkEnd, s));
     }
-    void* x = (ev->blocks % 2 == 1) ? ev->act[2].p : ev->act[0].p; // the buffer rotation of the layer list
-    ev->trunkOut = x;
-    Range headsRange("nsg.heads");
-    NSG_HIP(nsg::launchHeads(x, ev->W->heads.w.p, (const float*)ev->W->heads.bias.p, (float*)ev->policy.p, ev->vfeat.p, B,
-                             ev->F, ev->headsCout, ev->vc, ev->fc1K, ev->W->heads.accScale, prec, s));
-    const size_t partStride = (size_t)ev->batchMax * ev->vh;
-    NSG_HIP(nsg::launchDense(ev->vfeat.p, ev->W->fc1.w.p, (const float*)ev->W->fc1.bias.p, (float*)ev->hidden.p, B,
-                             ev->fc1K, ev->vh, partStride, ev->W->fc1.accScale, prec, s));
-    NSG_HIP(nsg::launchValueOut((const float*)ev->hidden.p, (const float*)ev->W->fc1.bias.p, nsg::denseSplits(ev->fc1K, prec),
-                                partStride, (const float*)ev->W->fc2W.p, (const float*)ev->W->fc2B.p, (float*)ev->value.p,
-                                (float*)ev->draw.p, B, ev->vh, s));
-    return NSG_OK;
+    return enqueueHeads(ev, trunkListOutput(ev), 0, B, nsg::kF16x3, s);
 }
 
-// The value / policy heads behind a trunk whose output is `x` (the tail of every forward).
-int enqueueHeads(nsg_evaluator* ev, void* x, int B, int hprec, hipStream_t s) {
-    Range headsRange("nsg.heads");
-    NSG_HIP(nsg::launchHeads(x, ev->W->heads.w.p, (const float*)ev->W->heads.bias.p, (float*)ev->policy.p, ev->vfeat.p, B,
-                             ev->F, ev->headsCout, ev->vc, ev->fc1K, ev->W->heads.accScale, hprec, s));
-    const size_t partStride = (size_t)ev->batchMax * ev->vh;
-    NSG_HIP(nsg::launchDense(ev->vfeat.p, ev->W->fc1.w.p, (const float*)ev->W->fc1.bias.p, (float*)ev->hidden.p, B,
-                             ev->fc1K, ev->vh, partStride, ev->W->fc1.accScale, hprec, s));
-    NSG_HIP(nsg::launchValueOut((const float*)ev->hidden.p, (const float*)ev->W->fc1.bias.p, nsg::denseSplits(ev->fc1K, hprec),
-                                partStride, (const float*)ev->W->fc2W.p, (const float*)ev->W->fc2B.p, (float*)ev->value.p,
-                                (float*)ev->draw.p, B, ev->vh, s));
-    return NSG_OK;
-}
-
-// The whole forward of a mid batch with the cooperative trunk (under the device's token: enqueueForward).
-int enqueueCoop(nsg_evaluator* ev, int B, const nsg::ConvPlan& plan, hipStream_t s, hipEvent_t trunkBegin, hipEvent_t trunkEnd) {
+// The whole forward of a mid batch with the cooperative trunk (under the device's token).
+int enqueueCoop(nsg_evaluator* ev, int B, const nsg::LaunchForm& form, hipStream_t s, hipEvent_t trunkBegin, hipEvent_t trunkEnd) {
     const int prec = ev->prec;
-    ev->lastTrunkPrec = prec;
     {
         Range r("nsg.planes");
         NSG_HIP(nsg::launchExtractBitsAct(ev->planes.p, (const uint64_t*)ev->input.p, B, ev->numChannels, ev->cpad, prec, s));
     }
     {
         Range r("nsg.trunk");
-        const int members = nsg::coopMembers(ev->F, plan);
-        bool stemFirst = false;
-        (void)nsg::canRunCoopTrunk(ev->F, ev->cpad, prec, plan, &stemFirst);
         // flag values count on across launches (24 bits; the array is cleared when they run out): no memset per forward
         if (ev->coopFlagBase + 256u >= (1u << 24)) {
             NSG_HIP(hipMemsetAsync(ev->coopFlags.p, 0, ev->coopFlags.bytes, s));
@@ -675,11 +686,10 @@ int enqueueCoop(nsg_evaluator* ev, int B, const nsg::ConvPlan& plan, hipStream_t
         }
         const unsigned flagBase = ev->coopFlagBase;
         ev->coopFlagBase += 128; // (more than any net's 3x3 layers: 1 + 2 x 40)
-        (void)members;
-        if (stemFirst) // the stem has fewer chunk pairs than the plan splits K by: its own launch, the plan's stem kernel
+        if (form.stemFirst) // the stem has fewer chunk pairs than the plan splits K by: its own launch, the plan's stem kernel
             NSG_HIP(nsg::launchConv3x3(ev->planes.p, ev->W->stem.w.p, (const float*)ev->W->stem.bias.p, nullptr, ev->act[0].p, B,
-                                       ev->cpad, ev->F, 1, ev->W->stem.accScale, prec, plan, s, nullptr, false));
-        const int l0 = stemFirst ? 1 : 0;
+                                       ev->cpad, ev->F, 1, ev->W->stem.accScale, prec, form.plan, s, nullptr, false));
+        const int l0 = form.stemFirst ? 1 : 0;
         if (trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
         // (test hook NSG_TEAM_FAULT_LAUNCHES: the last board's second member leaves at once and never publishes)
         // (NSG_COOP_FAULT_XCC_LAUNCHES: every board's second member claims another XCD, what a placement the hand-off
@@ -688,26 +698,44 @@ int enqueueCoop(nsg_evaluator* ev, int B, const nsg::ConvPlan& plan, hipStream_t
         if (faultBoard >= 0) --ev->teamFaultLaunches;
         else if (ev->coopFaultXccLaunches > 0) { faultBoard = -2; --ev->coopFaultXccLaunches; }
         NSG_HIP(nsg::launchCoopTrunk((const unsigned char*)ev->trunkLayers.p + (size_t)l0 * nsg::trunkLayerBytes(),
-                                     ev->trunkLayerCount - l0, B, ev->F, prec, plan, (unsigned*)ev->coopFlags.p, flagBase,
+                                     ev->trunkLayerCount - l0, B, ev->F, prec, form.plan, (unsigned*)ev->coopFlags.p, flagBase,
                                      ev->teamStatusDev, s, faultBoard));
         NSG_HIP(hipEventRecord(ev->teamDone, s));
         if (trunkEnd) NSG_HIP(hipEventRecord(trunkEnd, s));
     }
-    void* x = (ev->blocks % 2 == 1) ? ev->act[2].p : ev->act[0].p; // the buffer rotation of the layer list
-    ev->trunkOut = x;
-    return enqueueHeads(ev, x, B, nsg::headPrecision(prec), s);
+    return enqueueHeads(ev, trunkListOutput(ev), 0, B, nsg::headPrecision(prec), s);
 }
 
-// One chain = the whole forward for boards [off, off + count) on stream `s`.
-int enqueueChain(nsg_evaluator* ev, int off, int count, const nsg::ConvPlan& plan, hipStream_t s,
+// The team or the cooperative trunk.  Two such launches on one device could starve each other: under the device's token.
+int enqueuePersistent(nsg_evaluator* ev, int B, const nsg::LaunchForm& form, hipStream_t s, hipEvent_t trunkBegin,
+                      hipEvent_t trunkEnd) {
+    const bool team = form.kind == nsg::LaunchForm::Team;
+    TeamTokenGuard token(ev);
+    if (!token.held)
+        return fail(NSG_E_HIP, team ? "team trunk: hipStreamWaitEvent on the device's other team launch failed"
+                                    : "cooperative trunk: hipStreamWaitEvent on the device's other persistent launch failed");
+    return team ? enqueueTeam(ev, B, form.members, s, trunkBegin, trunkEnd) : enqueueCoop(ev, B, form, s, trunkBegin, trunkEnd);
+}
+
+// Every 3x3 layer in one persistent launch whose workgroups own whole boards (no hand-off).
+int enqueueWholeTrunk(nsg_evaluator* ev, int B, const nsg::ConvPlan& plan, hipStream_t s, hipEvent_t trunkBegin,
+                      hipEvent_t trunkEnd) {
+    const int prec = ev->prec;
+    NSG_HIP(nsg::launchExtractBitsAct(ev->planes.p, (const uint64_t*)ev->input.p, B, ev->numChannels, ev->cpad, prec, s));
+    if (trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
+    NSG_HIP(nsg::launchTrunk(ev->trunkLayers.p, ev->trunkLayerCount, B, prec, plan, s));
+    if (trunkEnd) NSG_HIP(hipEventRecord(trunkEnd, s));
+    return enqueueHeads(ev, trunkListOutput(ev), 0, B, nsg::headPrecision(prec), s);
+}
+
+// One chain = the whole forward for boards [off, off + count) on stream `s`, the trunk in `prec`: the evaluator's
+// precision, or kF16x3 -- the kF16x3 copy of the trunk -- where an MX evaluator's plan has no MX form (LaunchForm::trunkPrec).
+int enqueueChain(nsg_evaluator* ev, int off, int count, const nsg::ConvPlan& plan, int prec, hipStream_t s,
                  bool stampsOk, hipEvent_t trunkBegin = nullptr, hipEvent_t trunkEnd = nullptr) {
-    // kF16m8 runs full tiles only; smaller launch plans use the kF16x3 copy of the trunk
-    const bool x3Fallback = nsg::isMx(ev->prec) && (plan.nfrag != 4 || ev->W->outsideM8Window);
-    const int prec = x3Fallback ? (int)nsg::kF16x3 : ev->prec;
+    const bool x3Fallback = prec != ev->prec;
     const ConvLayer& stem = x3Fallback ? ev->W->stemX3 : ev->W->stem;
     const std::vector<ConvLayer>& conv1 = x3Fallback ? ev->W->conv1X3 : ev->W->conv1;
     const std::vector<ConvLayer>& conv2 = x3Fallback ? ev->W->conv2X3 : ev->W->conv2;
-    if (off == 0) ev->lastTrunkPrec = prec;
     const size_t es = (size_t)nsg::elemSize(prec);
     auto act = [&](void* base, size_t rowElems) { return (void*)((unsigned char*)base + (size_t)off * rowElems * es); };
     const uint64_t* input = (const uint64_t*)ev->input.p + (size_t)off * ev->numChannels * 2;
@@ -717,144 +745,39 @@ int enqueueChain(nsg_evaluator* ev, int off, int count, const nsg::ConvPlan& pla
         Range r("nsg.planes");
         NSG_HIP(nsg::launchExtractBitsAct(planes, input, count, ev->numChannels, ev->cpad, prec, s));
     }
-    Range trunkRange("nsg.trunk");
-    // stem + residual trunk
-    void* x = act(ev->act[0].p, (size_t)81 * ev->F);
-    void* y = act(ev->act[1].p, (size_t)81 * ev->F);
-    void* z = act(ev->act[2].p, (size_t)81 * ev->F);
     const int hprec = nsg::headPrecision(prec); // kF16m8: the last trunk layer writes the kF16x3 layout
-    NSG_HIP(nsg::launchConv3x3(planes, stem.w.p, (const float*)stem.bias.p, nullptr, x, count,
-                               ev->cpad, ev->F, 1, stem.accScale, prec, plan, s, nullptr,
-                               hprec != prec && ev->blocks == 0));
-    if (trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
-    for (int k = 0; k < ev->blocks; ++k) {
-        unsigned long long* st1 = nullptr;
-        unsigned long long* st2 = nullptr;
+    void* x = act(ev->act[0].p, (size_t)81 * ev->F);
+    {
+        Range trunkRange("nsg.trunk");
+        // stem + residual trunk
+        void* y = act(ev->act[1].p, (size_t)81 * ev->F);
+        void* z = act(ev->act[2].p, (size_t)81 * ev->F);
+        NSG_HIP(nsg::launchConv3x3(planes, stem.w.p, (const float*)stem.bias.p, nullptr, x, count,
+                                   ev->cpad, ev->F, 1, stem.accScale, prec, plan, s, nullptr,
+                                   hprec != prec && ev->blocks == 0));
+        if (trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
+        for (int k = 0; k < ev->blocks; ++k) {
+            unsigned long long* st1 = nullptr;
+            unsigned long long* st2 = nullptr;
 #ifdef NSG_DIAG_STAMPS
-        if (ev->stamps.p && stampsOk) {
-            st1 = (unsigned long long*)ev->stamps.p + (size_t)(2 * k) * 4096 * 8;
-            st2 = (unsigned long long*)ev->stamps.p + (size_t)(2 * k + 1) * 4096 * 8;
-        }
+            if (ev->stamps.p && stampsOk) {
+                st1 = (unsigned long long*)ev->stamps.p + (size_t)(2 * k) * 4096 * 8;
+                st2 = (unsigned long long*)ev->stamps.p + (size_t)(2 * k + 1) * 4096 * 8;
+            }
 #else
-        (void)stampsOk;
+            (void)stampsOk;
 #endif
-        NSG_HIP(nsg::launchConv3x3(x, conv1[k].w.p, (const float*)conv1[k].bias.p, nullptr, y, count,
-                                   ev->F, ev->F, 1, conv1[k].accScale, prec, plan, s, st1));
-        NSG_HIP(nsg::launchConv3x3(y, conv2[k].w.p, (const float*)conv2[k].bias.p, x, z, count,
-                                   ev->F, ev->F, 1, conv2[k].accScale, prec, plan, s, st2,
-                                   hprec != prec && k == ev->blocks - 1));
-        void* t = x; x = z; z = t;
-    }
-    if (trunkEnd) NSG_HIP(hipEventRecord(trunkEnd, s));
-    if (off == 0) ev->trunkOut = x;
-    if (trunkRange.on) { roctx().pop(); trunkRange.on = false; }
-    Range headsRange("nsg.heads");
-    // heads
-    float* policy = (float*)ev->policy.p + (size_t)off * NSG_MOVE_INDEX_MAX;
-    void* vfeat = act(ev->vfeat.p, (size_t)ev->fc1K);
-    float* hidden = (float*)ev->hidden.p + (size_t)off * ev->vh;
-    NSG_HIP(nsg::launchHeads(x, ev->W->heads.w.p, (const float*)ev->W->heads.bias.p, policy, vfeat, count, ev->F,
-                             ev->headsCout, ev->vc, ev->fc1K, ev->W->heads.accScale, hprec, s));
-    const size_t partStride = (size_t)ev->batchMax * ev->vh; // floats between the K slices' partial sums
-    NSG_HIP(nsg::launchDense(vfeat, ev->W->fc1.w.p, (const float*)ev->W->fc1.bias.p, hidden, count, ev->fc1K,
-                             ev->vh, partStride, ev->W->fc1.accScale, hprec, s));
-    NSG_HIP(nsg::launchValueOut(hidden, (const float*)ev->W->fc1.bias.p, nsg::denseSplits(ev->fc1K, hprec), partStride,
-                                (const float*)ev->W->fc2W.p, (const float*)ev->W->fc2B.p,
-                                (float*)ev->value.p + off, (float*)ev->draw.p + off, count, ev->vh, s));
-    return NSG_OK;
-}
-
-// The tile plan of a batch of B boards on this evaluator (precision, channel count, CU count, tuning).
-nsg::ConvPlan planForBatch(nsg_evaluator* ev, int B) {
-    nsg::ConvPlan plan = nsg::chooseConvPlan(B, ev->F, ev->prop.multiProcessorCount, ev->tuning);
-    // kF16m8 keeps four image buffers in LDS (125 KB for two boards): a CU holds one two-board
-    // workgroup, so where the channel count only allows two-wave workgroups (F = 384) one-board
-    // tiles (74 KB) keep all four SIMDs busy with two workgroups per CU
-    // (an F16M8 evaluator whose network left the fixed-scale window runs as kF16x3: none of the MX plans apply)
-    const bool mx = nsg::isMx(ev->prec) && !ev->W->outsideM8Window;
-    if (mx && plan.nfrag == 4 && plan.nwaves <= 2 && ev->tuning.nb == 0) plan.nb = 1;
-    // Mid batches -- the engine's default batch of 128 and its benchmark's 60..159 -- run kF16m8
-    // one-board tiles whose four waves are two row groups x two 64-channel groups (two workgroups per
-    // board) wherever those fill more than half the CUs in one round of workgroups
-    if (mx && plan.nfrag != 4 && ev->F % 128 == 0 && ev->tuning.nfrag == 0 &&
-        ev->tuning.msplit != 1) {
-        const long cus = ev->prop.multiProcessorCount;
-        const long wgM8 = (long)B * (ev->F / 128);
-        // (NSG_KSPLIT4_MAX_BATCH: experiment knob, read once -- largest batch that takes the four-way K split)
-        static const int k4max = [] { const char* e = getenv("NSG_KSPLIT4_MAX_BATCH"); return e ? atoi(e) : -1; }();
-        if (ev->F == 256 && ev->cpad == 128 && ev->tuning.msplit != 2 &&
-            (k4max >= 0 ? B <= k4max : (long)B * 4 <= cus)) {
-            // small batches: four workgroups per board, each one 64-channel group whose four waves take one chunk
-            // pair apiece (K split by four, whole board resident in LDS)
-            plan.nb = 1; plan.nfrag = 4; plan.nwaves = 4; plan.msplit = 1; plan.ksplit = 4;
-            // ... and while eight workgroups per board still fit the chip in one round, the rows are split
-            // over two workgroups as well (NSG_ROWSPLIT8_MAX_BATCH, read when the evaluator is created)
-            // -- two, three or six row groups of three, two or one fragment: as many as fit the chip in one round
-            const int k8max = ev->tuning.rowsplit8Max;
-            if (k8max >= 0 ? B <= k8max : true) {
-                // (three row groups = twelve workgroups per board: three boards' do not fit an XCD, so 17-21 boards have
-                // no cooperative form with them; two row groups as ONE cooperative launch beat three as per-layer
-                // launches by 2...9 %: profiles/r04/zn_*.  Without the cooperative trunk -- switched off, the device's
-                // lock lost, after a give-up -- three row groups it is.)
-                const bool coop = ev->coopEnabled && ev->prec == nsg::kF16m6 && ev->teamStatusDev && ev->coopFlags.p;
-                if ((long)B * 24 <= cus) plan.msplit = 6;
-                else if ((long)B * 12 <= cus && !coop) plan.msplit = 3;
-                else if ((long)B * 8 <= cus) plan.msplit = 2;
-            }
-        } else
-        if (wgM8 <= cus && wgM8 * 2 > cus) { // (measured: 1.17-1.29 ms for every B in 65..128; kF16x3 plans 1.26-1.54 ms)
-            plan.nb = 1; plan.nfrag = 4; plan.nwaves = 4; plan.msplit = 2;
-            // K split instead of the row split where the whole board fits in LDS (<= 256 channels) and both
-            // the stem's and the trunk's chunk pairs halve evenly; NSG_CONV_MSPLIT=2 keeps the row split
-            const int stemChunks = ev->cpad / 32, trunkChunks = ev->F / 32;
-            if (ev->tuning.msplit != 2 && trunkChunks <= 8 && trunkChunks % 4 == 0 && stemChunks % 4 == 0 && stemChunks <= 8) {
-                plan.msplit = 1;
-                plan.ksplit = 2;
-            }
+            NSG_HIP(nsg::launchConv3x3(x, conv1[k].w.p, (const float*)conv1[k].bias.p, nullptr, y, count,
+                                       ev->F, ev->F, 1, conv1[k].accScale, prec, plan, s, st1));
+            NSG_HIP(nsg::launchConv3x3(y, conv2[k].w.p, (const float*)conv2[k].bias.p, x, z, count,
+                                       ev->F, ev->F, 1, conv2[k].accScale, prec, plan, s, st2,
+                                       hprec != prec && k == ev->blocks - 1));
+            void* t = x; x = z; z = t;
         }
+        if (trunkEnd) NSG_HIP(hipEventRecord(trunkEnd, s));
+        if (off == 0) ev->trunkOut = x;
     }
-
-    // 192 channels (BASELINE configs[1]: 10x192 at batch 64) are three chunk pairs: up to CUs/3 boards run one
-    // 64-channel group per workgroup whose three waves take one pair each, all of the board's chunk tiles resident
-    // (the four-way K split of the 256-channel nets, three ways), the rows over as many workgroups as fit one round.
-    if (mx && ev->F == 192 && ev->cpad == 128 && ev->tuning.nb == 0 && ev->tuning.nfrag == 0 && ev->tuning.nwaves == 0 &&
-        ev->tuning.msplit != 2 && ev->tuning.ksplit3 != 0) {
-        const long cus = ev->prop.multiProcessorCount;
-        if ((long)B * 3 <= cus) {
-            plan = nsg::ConvPlan{};
-            plan.nb = 1; plan.nfrag = 4; plan.nwaves = 3; plan.msplit = 1; plan.ksplit = 3;
-            if (ev->tuning.msplit != 1) {
-                if ((long)B * 18 <= cus) plan.msplit = 6;
-                else if ((long)B * 9 <= cus) plan.msplit = 3;
-                else if ((long)B * 6 <= cus) plan.msplit = 2;
-            }
-        }
-    }
-
-    // Mid batches, MX arithmetic: two-board tiles of ONE 64-channel group (or two) per workgroup whose waves split
-    // every chunk pair's slabs between them (mfma_tile.h, OwnSeq) -- where one workgroup per (two boards, group)
-    // fills more than half the CUs in one round and the four-workgroups-per-board K split does not apply.  Against
-    // the one-board tiles it replaces: a workgroup streams half the weights for twice the boards, and the
-    // two-board tile's edge-packed rows need 19 % fewer matrix instructions per board.  MEASURED SLOWER (round 3,
-    // profiles/r03/d_*): 113k against 123k evals/s at 128 boards, 134k against 151k at 256 -- a wave's share of a
-    // chunk pair is 4.2k cycles of MFMAs, and the pair's two tile round trips, its barrier and the one-slab lead of
-    // the MX weight records no longer hide behind it.  Opt-in: NSG_SLAB_SPLIT=1.
-    if (mx && ev->tuning.slabSplit == 1 && ev->tuning.nb == 0 && ev->tuning.nfrag == 0 && ev->tuning.nwaves == 0 &&
-        ev->tuning.msplit == 0 && !(plan.ksplit == 4)) {
-        const long cus = ev->prop.multiProcessorCount;
-        const long tiles = (B + 1) / 2;
-        for (int ss : {4, 2}) {
-            if (ev->F % (256 / ss) != 0) continue;
-            const long wgs = tiles * (ev->F / (256 / ss));
-            if (wgs <= cus && wgs * 2 > cus) {
-                plan = nsg::ConvPlan{};
-                plan.nb = 2; plan.nfrag = 4; plan.nwaves = 4; plan.sslab = ss;
-                break;
-            }
-        }
-    }
-
-    return plan;
+    return enqueueHeads(ev, x, off, count, hprec, s);
 }
 
 // A forward pass of the general graph path: the plane expansion, the plan's launches in order, the output scatter.
@@ -904,32 +827,81 @@ int enqueueGraph(nsg_evaluator* ev, int B) {
     return NSG_OK;
 }
 
+// Chains and Parts: independent launch chains on separate streams, forked from and joined to `s` -- half-batch chains of
+// one plan, or a full part plus remainder parts with their own plans.
+int enqueueForked(nsg_evaluator* ev, int B, const nsg::LaunchForm& form, hipStream_t s, hipEvent_t trunkBegin,
+                  hipEvent_t trunkEnd) {
+    const bool isParts = form.kind == nsg::LaunchForm::Parts;
+    // stagger: measured layer time / chains (first forward of a launch shape runs unstaggered and is timed)
+    int delayUs = !isParts && (form.stagger || ev->chainDelayUs > 0) ? ev->chainDelayUs : 0;
+    bool calibrate = false;
+    if (delayUs < 0) {
+        if (ev->calibPending) { // the previous forward has been awaited: its events are complete
+            float ms = 0.f;
+            if (hipEventSynchronize(ev->calibEv[1]) == hipSuccess &&
+                hipEventElapsedTime(&ms, ev->calibEv[0], ev->calibEv[1]) == hipSuccess && ev->blocks > 0) {
+                ev->calibLayerUs = ms * 1000.f / (float)(2 * ev->blocks);
+                ev->calibKey = ev->calibPendingKey;
+            }
+            ev->calibPending = false;
+        }
+        const int wgPerChain = (form.per / 2) * std::max(1, ev->F / (form.plan.nwaves * form.plan.nfrag * 16));
+        const int rounds = (wgPerChain + ev->prop.multiProcessorCount - 1) / ev->prop.multiProcessorCount;
+        const int key = rounds * 16 + form.chains;
+        if (key == ev->calibKey && ev->calibLayerUs > 0.f) {
+            delayUs = (int)(ev->calibLayerUs / (float)form.chains + 0.5f);
+        } else {
+            delayUs = 0;
+            calibrate = ev->blocks > 0;
+            ev->calibPendingKey = key;
+        }
+    }
+    NSG_HIP(hipEventRecord(ev->forkEvent, s));
+    if (trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
+    for (int c = 0; c < form.chains; ++c) {
+        const int off = isParts ? form.parts[c].off : c * form.per;
+        const int count = isParts ? form.parts[c].count : std::min(form.per, B - off);
+        if (count <= 0) break;
+        hipStream_t cs = (c == 0) ? s : ev->chainStream[c - 1];
+        if (c > 0) NSG_HIP(hipStreamWaitEvent(cs, ev->forkEvent, 0));
+        if (c > 0 && delayUs > 0) {
+            hipLaunchKernelGGL(delayKernel, dim3(1), dim3(64), 0, cs, (unsigned long long)delayUs * 100ull * c);
+        }
+        const bool timeIt = calibrate && c == 0;
+        int rc = enqueueChain(ev, off, count, isParts ? form.parts[c].plan : form.plan,
+                              isParts ? form.parts[c].trunkPrec : form.trunkPrec, cs, c == 0,
+                              timeIt ? ev->calibEv[0] : nullptr, timeIt ? ev->calibEv[1] : nullptr);
+        if (rc) return rc;
+        if (timeIt) ev->calibPending = true;
+        if (c > 0) {
+            NSG_HIP(hipEventRecord(ev->joinEvent[c - 1], cs));
+            NSG_HIP(hipStreamWaitEvent(s, ev->joinEvent[c - 1], 0));
+        }
+    }
+    if (trunkEnd) NSG_HIP(hipEventRecord(trunkEnd, s));
+    return NSG_OK;
+}
+
+// What the nsg_get_last_* getters report of a forward that takes `form`.
+void recordLaunchForm(nsg_evaluator* ev, const nsg::LaunchForm& form) {
+    ev->lastPersistent = form.kind == nsg::LaunchForm::Team ? 1 : form.kind == nsg::LaunchForm::Coop ? 2 : 0;
+    ev->teamLast = ev->lastPersistent != 0;
+    ev->lastWholeTrunk = form.kind == nsg::LaunchForm::WholeTrunk ? 1 : 0;
+    ev->lastParts = form.nParts;
+    ev->lastPlan = form.plan;
+    ev->lastChains = form.chains;
+    ev->lastTrunkPrec = form.trunkPrec;
+}
+
+// A forward pass: WHICH launches a batch of n boards takes is chooseLaunchForm's business (launch_form.h); this issues them.
 int enqueueForward(nsg_evaluator* ev, size_t n) {
     const int B = (int)n;
     ++ev->statBatches;
     ev->statPositions += n;
     if (ev->G) return enqueueGraph(ev, B); // the general graph path: none of the plan / team / chain logic below
     hipStream_t s = ev->stream;
-    // the tile plan is chosen for the whole batch: all chains run concurrently
-    nsg::ConvPlan plan = planForBatch(ev, B);
-    const bool mx = nsg::isMx(ev->prec) && !ev->W->outsideM8Window;
-    const bool prof = ev->profile;
-    if (prof && ev->evUsed + 4 > (int)ev->ev.size()) {
-        int rc = drainProfile(ev);
-        if (rc) return rc;
-    }
-    hipEvent_t* e = prof ? &ev->ev[ev->evUsed] : nullptr;
-    if (prof) NSG_HIP(hipEventRecord(e[0], s));
-
-    // The smallest batches: every 3x3 layer in one persistent launch, a board per team of 16-96 workgroups
-    // (kernels/team_trunk.hip), when no tuning override asks for a particular per-layer plan and no other evaluator
-    // has a team launch in flight on this device.
-    ev->teamLast = false;
-    ev->lastPersistent = 0;
-    ev->lastWholeTrunk = 0;
-    ev->lastParts = 0;
-    // (a give-up word still raised here belongs to a forward nobody waited for: its batch is gone, the team path is not
-    // taken again)
+    // (a give-up word still raised here belongs to a forward nobody waited for: its batch is gone, neither persistent
+    // path is taken again)
     if (ev->teamStatusHost && *ev->teamStatusHost != 0) {
         *ev->teamStatusHost = 0;
         ev->teamEnabled = 0;
@@ -937,212 +909,32 @@ int enqueueForward(nsg_evaluator* ev, size_t n) {
         ++ev->teamFallbacks;
         releaseTeamToken(ev);
     }
-    const int members = (ev->tuning.nb == 0 && ev->tuning.nfrag == 0 && ev->tuning.nwaves == 0 && ev->tuning.msplit == 0 &&
-                         ev->useTrunkKernel != 1) ? teamMembersFor(ev, B) : 0;
-    if (members > 0) {
-        int rc;
-        {
-            TeamTokenGuard token(ev);
-            if (!token.held) return fail(NSG_E_HIP, "team trunk: hipStreamWaitEvent on the device's other team launch failed");
-            rc = enqueueTeam(ev, B, members, s, prof ? e[1] : nullptr, prof ? e[2] : nullptr);
-        }
-        if (rc) return rc;
-        ev->teamLast = true;
-        ev->lastPersistent = 1;
-        plan = nsg::ConvPlan{};
-        plan.nb = 1; plan.nfrag = 1; plan.nwaves = 8; plan.ksplit = 8; // 16 weight fragments x 2 or 6 row groups per board, K over 8 waves
-        plan.msplit = members / (ev->F / 16); // row groups
-        ev->lastPlan = plan;
-        ev->lastChains = 1;
-        if (prof) {
-            NSG_HIP(hipEventRecord(e[3], s));
-            ev->evUsed += 4;
-            ev->pendingTrunkLaunchesPerFwd = 1;
-        }
-        return NSG_OK;
-    }
+    const nsg::LaunchForm form = nsg::chooseLaunchForm(launchConfigOf(ev), B);
+    recordLaunchForm(ev, form);
 
-    // Mid batches on the two-way K split: the cooperative trunk, when every workgroup of its grid is resident at once
-    // (same token as the team trunk: one such launch per device at a time)
-    if (ev->coopEnabled && ev->teamStatusDev && ev->coopFlags.p && ev->tuning.nb == 0 && ev->tuning.nfrag == 0 &&
-        ev->tuning.nwaves == 0 && ev->tuning.msplit == 0 && ev->useTrunkKernel != 1 && mx && ev->chainMinBatch <= 0 &&
-        ev->chainDelayUs == 0 && nsg::canRunCoopTrunk(ev->F, ev->cpad, ev->prec, plan) &&
-        nsg::coopFits(B, nsg::coopMembers(ev->F, plan), ev->prop.multiProcessorCount) &&
-        ev->trunkLayerCount < 127 && // (a launch's flag values fit the 128 the base advances by)
-        // measured: 256 channels with up to eight members per board +1...8 % (24-128 boards;
-        // profiles/r04/o_cooperative_trunk_all_k_split_plans_sweep.txt; twelve members, 17-21 boards, do not fit an
-        // XCD's CUs three boards at a time); 192 channels +1...9 % (17-80 boards) since the hand-off stays in the XCD's L2
-        // (profiles/r04/zd_cooperative_trunk_192_channels.txt; -2...-8 % with write-through stores)
-        (ev->coopForced || (ev->F == 256 && nsg::coopMembers(ev->F, plan) <= 8) || ev->F == 192)) {
-        int rc;
-        {
-            TeamTokenGuard token(ev);
-            if (!token.held) return fail(NSG_E_HIP, "cooperative trunk: hipStreamWaitEvent on the device's other persistent launch failed");
-            rc = enqueueCoop(ev, B, plan, s, prof ? e[1] : nullptr, prof ? e[2] : nullptr);
-        }
+    const bool prof = ev->profile;
+    if (prof && ev->evUsed + 4 > (int)ev->ev.size()) {
+        int rc = drainProfile(ev);
         if (rc) return rc;
-        ev->teamLast = true;
-        ev->lastPersistent = 2;
-        ev->lastPlan = plan;
-        ev->lastChains = 1;
-        if (prof) {
-            NSG_HIP(hipEventRecord(e[3], s));
-            ev->evUsed += 4;
-            ev->pendingTrunkLaunchesPerFwd = 1;
-        }
-        return NSG_OK;
     }
-
-    // A batch with more tiles than CUs runs as two independent chains of half-batch
-    // launches on separate streams: boards never interact, so chain A's layer l+1 may
-    // start while chain B is still in layer l.  The partly filled last round of
-    // workgroups of one chain's launch is topped up by the other chain's launch instead
-    // of idling the chip (B=640: 82.7k -> 111.6k evals/s; B=1024: 113.8k -> 119.7k).
-    // With NSG_CHAIN_DELAY_US set, two staggered chains (below) also run when all tiles are resident at
-    // once on more than half the chip (B = 512 on 256 CUs; not the f32 kernel, which is matrix-bound at
-    // 0.85 of its peak and loses 2 %).  With more tiles than CUs the chains compete for CUs and topping-up
-    // matters more than phase: those always run unstaggered (staggered B = 640 loses 2 %).
-    const int cus = ev->prop.multiProcessorCount;
-    const int tiles = ((B + 1) / 2) * std::max(1, ev->F / (plan.nwaves * plan.nfrag * 16)); // of a 2-board plan
-    const bool oneRound = tiles <= cus;
-    int chains = 1;
-    if (plan.nb == 2) {
-        if (ev->chainMinBatch > 0) chains = B >= ev->chainMinBatch ? ev->numChains : 1;
-        else if (!oneRound) chains = ev->numChains;
-        else if (2 * tiles > cus && ev->chainDelayUs != 0 && ev->prec != nsg::kFp32) chains = std::min(ev->numChains, 2);
+    hipEvent_t* e = prof ? &ev->ev[ev->evUsed] : nullptr;
+    hipEvent_t trunkBegin = prof ? e[1] : nullptr, trunkEnd = prof ? e[2] : nullptr;
+    if (prof) NSG_HIP(hipEventRecord(e[0], s));
+    int rc = NSG_OK;
+    switch (form.kind) {
+    case nsg::LaunchForm::Team:
+    case nsg::LaunchForm::Coop: rc = enqueuePersistent(ev, B, form, s, trunkBegin, trunkEnd); break;
+    case nsg::LaunchForm::WholeTrunk: rc = enqueueWholeTrunk(ev, B, form.plan, s, trunkBegin, trunkEnd); break;
+    case nsg::LaunchForm::Parts:
+    case nsg::LaunchForm::Chains: rc = enqueueForked(ev, B, form, s, trunkBegin, trunkEnd); break;
+    case nsg::LaunchForm::Single: rc = enqueueChain(ev, 0, B, form.plan, form.trunkPrec, s, true, trunkBegin, trunkEnd); break;
     }
-    const bool stagger = oneRound && chains > 1;
-    bool trunkWanted = ev->useTrunkKernel == 1;
-    if (ev->useTrunkKernel < 0 && ev->prec == nsg::kF16m6 && plan.nfrag == 4 && ev->tuning.nb == 0 && ev->tuning.nfrag == 0 &&
-        ev->tuning.nwaves == 0 && ev->tuning.msplit == 0 && ev->chainMinBatch <= 0 && ev->chainDelayUs == 0) {
-        const long t = (B + plan.nb - 1) / plan.nb; // tiles = workgroups of the persistent launch
-        trunkWanted = t <= cus && (plan.nb == 1 ? t * 16 >= (long)cus * 9 : t * 4 >= (long)cus * 3);
-    }
-    const bool trunkKernel = trunkWanted && !ev->W->outsideM8Window && nsg::canRunTrunk(ev->F, plan);
-    if (trunkKernel) chains = 1;
-    const int per = ((B + chains - 1) / chains + 1) / 2 * 2; // boards per chain, whole 2-board tiles
-    ev->lastPlan = plan;
-    ev->lastChains = chains;
-
-    // Two-part batches.  Between the sizes whose plans fill the chip exactly, one plan for the whole batch leaves
-    // CUs idle (B = CUs/2 + 1 .. CUs as one-board tiles: one workgroup per board) or pays a two-board tile for a
-    // half-empty chip (B = CUs + 1 ..).  Boards never interact, so such a batch runs as a FULL part with the plan of
-    // the size below (CUs/2 boards, two-way K split; CUs boards, one-board tiles) plus the remainder with ITS plan
-    // (up to CUs/4 boards: the K split by four), on two streams like the half-batch chains above.
-    struct Part { int off, count; nsg::ConvPlan plan; };
-    Part parts[3];
-    int nParts = 0;
-    if (mx && !trunkKernel && ev->numChains >= 2 && ev->tuning.splitBatch != 0 && ev->F == 256 && ev->cpad == 128 &&
-        ev->tuning.nb == 0 && ev->tuning.nfrag == 0 && ev->tuning.nwaves == 0 && ev->tuning.msplit == 0 &&
-        ev->chainMinBatch <= 0 && ev->chainDelayUs == 0) {
-        // (measured on 256 CUs, profiles/r02/n_ab_two_part_batches.txt: 129 +10.6 %, 144 +7.7 %, 168 +5.7 %, 176 +2.5 %,
-        // 192 -5.9 %; 257 +52 %, 288 +37 %, 320 +27 %, 352 +18 %, 368 +14 %, 384 -7 %: from 3/2 of the CUs on
-        // the two-board tiles cover three quarters of the chip and win)
-        int off = 0, rem = B;
-        auto take = [&](int count) { parts[nParts++] = Part{off, count, planForBatch(ev, count)}; off += count; rem -= count; };
-        // more two-board tiles than CUs: one full chip of them first, the rest by the rules below (instead of two
-        // half-batch chains; only just above 2 CUs boards: 513-576 +2-3.5 %, from 640 on the two chains are 3-11 %
-        // faster, profiles/r02/n_ab_two_part_batches.txt)
-        if (rem > 2 * cus && rem <= ev->tuning.splitBatchMax3 * cus / 4) take(2 * cus);
-        if (rem > cus && rem < cus + cus / 2) take(cus);
-        else if (rem > cus / 2 && rem <= cus / 2 + 3 * cus / 16) take(cus / 2);
-        if (nParts > 0 && rem > 0) take(rem);
-        if (nParts < 2) nParts = 0;
-    }
-    if (nParts > 0) {
-        ev->lastPlan = parts[0].plan;
-        ev->lastChains = nParts;
-        ev->lastParts = nParts;
-        NSG_HIP(hipEventRecord(ev->forkEvent, s));
-        if (prof) NSG_HIP(hipEventRecord(e[1], s));
-        for (int c = 0; c < nParts; ++c) {
-            hipStream_t cs = (c == 0) ? s : ev->chainStream[c - 1];
-            if (c > 0) NSG_HIP(hipStreamWaitEvent(cs, ev->forkEvent, 0));
-            int rc = enqueueChain(ev, parts[c].off, parts[c].count, parts[c].plan, cs, c == 0);
-            if (rc) return rc;
-            if (c > 0) {
-                NSG_HIP(hipEventRecord(ev->joinEvent[c - 1], cs));
-                NSG_HIP(hipStreamWaitEvent(s, ev->joinEvent[c - 1], 0));
-            }
-        }
-        if (prof) NSG_HIP(hipEventRecord(e[2], s));
-    } else
-    if (chains == 1 && trunkKernel) {
-        // one persistent launch for all 2N+1 3x3 layers (measured slower; NSG_TRUNK_KERNEL=1)
-        const int prec = ev->prec;
-        ev->lastWholeTrunk = 1;
-        NSG_HIP(nsg::launchExtractBitsAct(ev->planes.p, (const uint64_t*)ev->input.p, B, ev->numChannels,
-                                          ev->cpad, prec, s));
-        if (prof) NSG_HIP(hipEventRecord(e[1], s));
-        NSG_HIP(nsg::launchTrunk(ev->trunkLayers.p, ev->trunkLayerCount, B, prec, plan, s));
-        if (prof) NSG_HIP(hipEventRecord(e[2], s));
-        void* x = (ev->blocks % 2 == 1) ? ev->act[2].p : ev->act[0].p;
-        ev->trunkOut = x;
-        ev->lastTrunkPrec = prec;
-        NSG_HIP(nsg::launchHeads(x, ev->W->heads.w.p, (const float*)ev->W->heads.bias.p, (float*)ev->policy.p,
-                                 ev->vfeat.p, B, ev->F, ev->headsCout, ev->vc, ev->fc1K, ev->W->heads.accScale, nsg::headPrecision(prec), s));
-        const size_t partStride = (size_t)ev->batchMax * ev->vh;
-        NSG_HIP(nsg::launchDense(ev->vfeat.p, ev->W->fc1.w.p, (const float*)ev->W->fc1.bias.p, (float*)ev->hidden.p,
-                                 B, ev->fc1K, ev->vh, partStride, ev->W->fc1.accScale, nsg::headPrecision(prec), s));
-        NSG_HIP(nsg::launchValueOut((const float*)ev->hidden.p, (const float*)ev->W->fc1.bias.p,
-                                    nsg::denseSplits(ev->fc1K, nsg::headPrecision(prec)), partStride, (const float*)ev->W->fc2W.p,
-                                    (const float*)ev->W->fc2B.p, (float*)ev->value.p, (float*)ev->draw.p, B, ev->vh, s));
-    } else if (chains == 1) {
-        int rc = enqueueChain(ev, 0, B, plan, s, true, prof ? e[1] : nullptr, prof ? e[2] : nullptr);
-        if (rc) return rc;
-    } else {
-        // stagger: measured layer time / chains (first forward of a launch shape runs unstaggered and is timed)
-        int delayUs = (stagger || ev->chainDelayUs > 0) ? ev->chainDelayUs : 0;
-        bool calibrate = false;
-        if (delayUs < 0) {
-            if (ev->calibPending) { // the previous forward has been awaited: its events are complete
-                float ms = 0.f;
-                if (hipEventSynchronize(ev->calibEv[1]) == hipSuccess &&
-                    hipEventElapsedTime(&ms, ev->calibEv[0], ev->calibEv[1]) == hipSuccess && ev->blocks > 0) {
-                    ev->calibLayerUs = ms * 1000.f / (float)(2 * ev->blocks);
-                    ev->calibKey = ev->calibPendingKey;
-                }
-                ev->calibPending = false;
-            }
-            const int wgPerChain = (per / 2) * std::max(1, ev->F / (plan.nwaves * plan.nfrag * 16));
-            const int rounds = (wgPerChain + ev->prop.multiProcessorCount - 1) / ev->prop.multiProcessorCount;
-            const int key = rounds * 16 + chains;
-            if (key == ev->calibKey && ev->calibLayerUs > 0.f) {
-                delayUs = (int)(ev->calibLayerUs / (float)chains + 0.5f);
-            } else {
-                delayUs = 0;
-                calibrate = ev->blocks > 0;
-                ev->calibPendingKey = key;
-            }
-        }
-        NSG_HIP(hipEventRecord(ev->forkEvent, s));
-        if (prof) NSG_HIP(hipEventRecord(e[1], s));
-        for (int c = 0; c < chains; ++c) {
-            const int off = c * per;
-            const int count = std::min(per, B - off);
-            if (count <= 0) break;
-            hipStream_t cs = (c == 0) ? s : ev->chainStream[c - 1];
-            if (c > 0) NSG_HIP(hipStreamWaitEvent(cs, ev->forkEvent, 0));
-            if (c > 0 && delayUs > 0) {
-                hipLaunchKernelGGL(delayKernel, dim3(1), dim3(64), 0, cs, (unsigned long long)delayUs * 100ull * c);
-            }
-            const bool timeIt = calibrate && c == 0;
-            int rc = enqueueChain(ev, off, count, plan, cs, c == 0, timeIt ? ev->calibEv[0] : nullptr,
-                                  timeIt ? ev->calibEv[1] : nullptr);
-            if (rc) return rc;
-            if (timeIt) ev->calibPending = true;
-            if (c > 0) {
-                NSG_HIP(hipEventRecord(ev->joinEvent[c - 1], cs));
-                NSG_HIP(hipStreamWaitEvent(s, ev->joinEvent[c - 1], 0));
-            }
-        }
-        if (prof) NSG_HIP(hipEventRecord(e[2], s));
-    }
+    if (rc) return rc;
     if (prof) {
         NSG_HIP(hipEventRecord(e[3], s));
         ev->evUsed += 4;
-        // launches bracketed by e[1]..e[2]: the 2N residual convs, or the ONE persistent launch (stem + 2N convs)
-        ev->pendingTrunkLaunchesPerFwd = (chains == 1 && trunkKernel) ? 1 : 2 * ev->blocks;
+        // launches bracketed by e[1]..e[2]: the 2N residual convs, or the ONE persistent launch
+        ev->pendingTrunkLaunchesPerFwd = form.trunkLaunchesPerFwd;
     }
     return NSG_OK;
 }
@@ -2034,6 +1826,28 @@ int nsg_get_last_slab_split(nsg_evaluator* ev, int* slab_split) {
 int nsg_get_last_trunk_precision(nsg_evaluator* ev, int* precision) {
     if (!ev || !precision) return fail(NSG_E_INVALID, "null argument");
     *precision = ev->lastTrunkPrec;
+    return NSG_OK;
+}
+
+int nsg_get_launch_form(nsg_evaluator* ev, int batch, int* kind, int* whole_trunk, int* parts, int* nb, int* nfrag,
+                        int* nwaves, int* chains, int* row_split, int* k_split, int* slab_split, int* precision) {
+    if (!ev) return fail(NSG_E_INVALID, "null evaluator");
+    if (!ev->loaded) return fail(NSG_E_NOT_LOADED, "no network loaded");
+    if (batch <= 0 || batch > ev->batchMax) return fail(NSG_E_INVALID, "batch %d outside 1..%d", batch, ev->batchMax);
+    nsg::LaunchForm f; // (the general graph path: what enqueueGraph reports)
+    if (!ev->G) f = nsg::chooseLaunchForm(launchConfigOf(ev), batch);
+    else f.chains = 0;
+    if (kind) *kind = f.kind == nsg::LaunchForm::Team ? 1 : f.kind == nsg::LaunchForm::Coop ? 2 : 0;
+    if (whole_trunk) *whole_trunk = f.kind == nsg::LaunchForm::WholeTrunk ? 1 : 0;
+    if (parts) *parts = f.nParts;
+    if (nb) *nb = f.plan.nb;
+    if (nfrag) *nfrag = f.plan.nfrag;
+    if (nwaves) *nwaves = f.plan.nwaves;
+    if (chains) *chains = f.chains;
+    if (row_split) *row_split = f.plan.nb ? f.plan.msplit : 0;
+    if (k_split) *k_split = f.plan.nb ? f.plan.ksplit : 0;
+    if (slab_split) *slab_split = f.plan.nb ? f.plan.sslab : 0;
+    if (precision) *precision = f.trunkPrec;
     return NSG_OK;
 }
 

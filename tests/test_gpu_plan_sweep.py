@@ -1,10 +1,12 @@
 """Every board of every launch plan against the float64 reference (tests/ref64.py).
 
 On one device the evaluator picks among some fifteen launch forms by batch size, channel count, precision and CU
-count (planForBatch / enqueueForward in nsg_capi.hip, chooseConvPlan in kernels/tile_launch.hip).  Each row of the
-matrix below is ONE evaluator run through batch sizes derived from info()["compute_units"] -- n - 1, n, n + 1 of
-every threshold of those functions -- ascending, then descending, as the engine's varying batches would.  Every
-forward of the ascending pass is checked board by board against ref64 (policy, value, draw, and the trunk), with the
+count: chooseLaunchForm in csrc/launch_form.cc (with planForBatch and chooseConvPlan), whose decisions
+tests/golden/launch_forms.txt tabulates on the CPU.  Each row of the matrix below is ONE evaluator run through batch sizes
+derived from info()["compute_units"] -- n - 1, n, n + 1 of every threshold of those functions -- ascending, then
+descending, as the engine's varying batches would.  Before every forward of the ascending pass the test reads what
+chooseLaunchForm says of the batch (Evaluator.launch_form), and what the forward then reports must be exactly that: the
+table is what the device runs.  Every forward of that pass is checked board by board against ref64 (policy, value, draw, and the trunk), with the
 localisation check on top of the absolute tolerance; the descending pass and a forward with the boards in reversed
 slots must be bit-identical to it (two-part batches, whose parts run different plans: within the tolerance).  Each
 row then asserts that every launch form FORMS says it can reach was reached, and that no persistent launch gave up.
@@ -61,16 +63,16 @@ def _sizes(cus, F, kind, top):
     return sorted(b for b in s if 1 <= b <= top)
 
 
-# ---- launch forms: name -> (the condition in nsg_capi.hip / tile_launch.hip that selects it, reachable(row, cus))
+# ---- launch forms: name -> (the condition of chooseLaunchForm / planForBatch in launch_form.cc that selects it, reachable(row, cus))
 def _mx(r):
     return r["prec"] in ("f16m8", "f16m6")
 
 
 FORMS = {
-    "team trunk": ("enqueueForward: teamMembersFor(ev, B) > 0 -- MX or f16x3, 192/256 channels, B <= kTeamMaxBoards "
+    "team trunk": ("chooseLaunchForm: Team, teamAvailable and teamMembers > 0 -- MX or f16x3, 192/256 channels, B <= kTeamMaxBoards "
                    "and B x F/16 x row groups <= CUs",
                    lambda r, cus: (_mx(r) or r["prec"] == "f16x3") and r["F"] in (192, 256) and not _off(r, "TEAM")),
-    "coop K2": ("enqueueForward: coopEnabled && canRunCoopTrunk (f16m6, 256 ch.) && coopFits, on planForBatch's K2 "
+    "coop K2": ("chooseLaunchForm: Coop, coopAvailable && canRunCoopTrunk (f16m6, 256 ch.) && coopFits, on planForBatch's K2 "
                 "window (CUs/4 < B <= CUs/2)",
                 lambda r, cus: r["prec"] == "f16m6" and r["F"] == 256 and r["kind"] == "full"),
     "coop K4 x1": ("... planForBatch's four-way K split (B x 4 <= CUs), one row group",
@@ -78,9 +80,9 @@ FORMS = {
     "coop K4 x2": ("... two row groups (B x 8 <= CUs); with the cooperative trunk three row groups give way to two",
                    lambda r, cus: r["prec"] == "f16m6" and r["F"] == 256 and not _off(r, "COOP") and cus // 8 > 1),
     "coop K4 x3": ("NOT CHOSEN BY DEFAULT: 256 channels take the cooperative trunk up to 8 members per board only "
-                   "(coopMembers <= 8 in enqueueForward); NSG_COOP_TRUNK=1 forces it", lambda r, cus: False),
+                   "(coopMembers <= 8 in chooseLaunchForm); NSG_COOP_TRUNK=1 forces it", lambda r, cus: False),
     "coop K4 x6": ("NOT CHOSEN BY DEFAULT: 24 members per board, as coop K4 x3", lambda r, cus: False),
-    "coop K3 x1": ("enqueueForward: 192 channels, planForBatch's three-way K split (B x 3 <= CUs), one row group, "
+    "coop K3 x1": ("chooseLaunchForm: Coop, 192 channels, planForBatch's three-way K split (B x 3 <= CUs), one row group, "
                    "coopFits (ceil(B / 8) x 3 members <= CUs / 8)",
                    lambda r, cus: r["prec"] == "f16m6" and r["F"] == 192 and r["kind"] == "full"),
     "coop K3 x2": ("... two row groups (B x 6 <= CUs), 6 members",
@@ -108,14 +110,14 @@ FORMS = {
     "per-layer K2": ("planForBatch: the K2 window on per-layer launches (f16m8; 128 channels)",
                      lambda r, cus: (r["prec"] == "f16m8" and r["F"] == 256 and r["kind"] == "full") or
                      (_mx(r) and r["F"] == 128 and r["kind"] == "short")),
-    "whole trunk nb1": ("enqueueForward: trunkKernel -- f16m6, canRunTrunk, one-board tiles, 9/16 CUs <= B <= CUs",
+    "whole trunk nb1": ("chooseLaunchForm: WholeTrunk -- f16m6, canRunTrunk, one-board tiles, 9/16 CUs <= B <= CUs",
                         lambda r, cus: r["prec"] == "f16m6" and r["F"] in (192, 256) and r["kind"] == "full"),
     "whole trunk nb2": ("... two-board tiles, 3/4 CUs <= tiles <= CUs",
                         lambda r, cus: r["prec"] == "f16m6" and r["F"] in (192, 256) and r["kind"] == "full"),
-    "two-part batch": ("enqueueForward: nParts > 0 -- MX, 256 ch., not trunkKernel, CUs/2 < B <= CUs/2 + 3 CUs/16, "
+    "two-part batch": ("chooseLaunchForm: Parts -- MX, 256 ch., not trunkKernel, CUs/2 < B <= CUs/2 + 3 CUs/16, "
                        "CUs < B < 3/2 CUs, or 2 CUs < B <= 9/4 CUs",
                        lambda r, cus: _mx(r) and r["F"] == 256 and r["kind"] == "full"),
-    "half-batch chains": ("enqueueForward: chains > 1 -- two-board plan with more tiles than CUs, no two-part split",
+    "half-batch chains": ("chooseLaunchForm: Chains -- two-board plan with more tiles than CUs, no two-part split",
                           lambda r, cus: (r["F"] in (192, 256) and r["kind"] == "full") or r["kind"] == "handful" or
                           (r["F"] == 384 and r["kind"] == "conv")),
     "tiles nfrag 1": ("chooseConvPlan: one fragment per wave, two-board tiles",
@@ -125,7 +127,7 @@ FORMS = {
     "tiles nfrag 4": ("chooseConvPlan: full tiles (waves cover 3/4 of the SIMDs)",
                       lambda r, cus: r["kind"] in ("conv", "short", "handful") or
                       (r["kind"] == "full" and not (r["prec"] == "f16m6" and r["F"] == 256))),
-    "f16x3 fallback of MX": ("enqueueChain: x3Fallback -- an f16m8 / f16m6 evaluator whose plan has no MX form "
+    "f16x3 fallback of MX": ("chooseLaunchForm: trunkPrec -- an f16m8 / f16m6 evaluator whose plan has no MX form "
                              "(plan.nfrag != 4) runs the f16x3 copy of its trunk",
                              lambda r, cus: _mx(r) and r["kind"] in ("full", "short")),
 }
@@ -253,9 +255,11 @@ def test_plan_sweep(nsg, oracle, pool, monkeypatch, prec, F, kind, env):
     seen, per_size, stats, errs = {}, {}, {}, {}
     try:
         for n in sizes:  # ascending: every board against ref64, and the same boards in reversed slots
+            foretold = ev.launch_form(n)
             dig, out, err = _check(ev, prec, n, bb, ref, stats)
             kind_, _ = ev.last_launch_kind()
             form, plan = ev.last_launch_form(), ev.last_plan()
+            assert (kind_, form, plan) == foretold, f"B={n}: ran {(kind_, form, plan)}, chooseLaunchForm said {foretold}"
             name = form_of(prec, kind_, form, plan)
             per_size[n] = (dig, name, kind_, form["whole_trunk"], form["parts"], plan["chains"], plan)
             seen.setdefault(name, []).append(n)
