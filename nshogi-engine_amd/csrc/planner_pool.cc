@@ -47,7 +47,6 @@ void Planner::pool(const Node& N) {
     if (Ks[0] < 1 || Ks[1] < 1 || Ks[0] > 9 || Ks[1] > 9 || Ks[0] % 2 == 0 || Ks[1] % 2 == 0)
         fail(N, "a " + KStr + " kernel: only odd kernel sizes from 1 to 9 each way");
     if (Ceil) fail(N, "ceil_mode 1: only ceil_mode 0");
-    if (!Max && Dil != std::vector<int64_t>{1, 1}) fail(N, "a dilated AveragePool: dilations on MaxPool only");
     const int KH = (int)Ks[0], KW = (int)Ks[1];
     const int DH = KH == 1 ? 1 : (int)std::min<int64_t>(Dil[0], 64), DW = KW == 1 ? 1 : (int)std::min<int64_t>(Dil[1], 64);
     const int Hy = DH * (KH - 1) / 2, Hx = DW * (KW - 1) / 2;
