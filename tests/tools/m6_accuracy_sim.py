@@ -5,7 +5,8 @@ E8M0 scale per 32 input channels -- per (position, chunk) for the activation cop
 channel, tap, chunk) for the weight copies -- which v_mfma_scale_f32_16x16x128_f8f6f4 applies for
 free and retires in HALF the cycles of its e4m3 form (profiles/r02/a_fp6_probe.txt): 1.5 instead
 of 2.0 MFMA units per MAC.  Scale rule: the OCP MX one, 2^(floor(log2(max|v|)) - 2), values beyond
-7.5 saturate.  Prints max/rms error of the policy logits against float64."""
+7.5 saturate.  Prints max/rms error of the policy logits against float64.
+An accuracy tool: tests/split_models.py is the authoritative bit-level statement of the format."""
 import importlib, json, sys, numpy as np, torch, torch.nn.functional as F
 import os; ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 nsg = importlib.import_module('nshogi-engine_amd'); import oracle_lib
