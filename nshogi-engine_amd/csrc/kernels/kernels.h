@@ -41,28 +41,14 @@ namespace nsg {
 // exponent as the block's last dword, mfma_tile.h kSplitRead)
 // (enum Precision, isMx, headPrecision: launch_form.h)
 constexpr int kM8LoShift = 12;   // stored lo byte = e4m3(lo * 2^12)
-constexpr int kM8WLoShift = 10;  // weight record  = e4m3(w_lo * 2^10)
-constexpr int kM8WHiShift = -2;  // weight record  = e4m3(w_hi * 2^-2); both products carry 2^-10
+// (kM8WLoShift, kM8WHiShift: launch_form.h)
 constexpr int kM8ScaleByte = 127 - 10; // E8M0 block scale of the weight operand
 
-// Bytes one activation channel occupies (a kF16x3 pair is 2 + 2 bytes, kF16m8 2 + 1 + 1).
-inline int elemSize(int prec) { return (prec == kFp32 || prec == kF16x3 || isMx(prec)) ? 4 : 2; }
-// Channels per 128-byte K chunk of the trunk convolution.
-inline int chunkChannels(int prec) { return 128 / elemSize(prec); }
+// (elemSize, chunkChannels, recordsPerTap, recordsPerChunk, inputChannelGranule, tileWeightRecords, denseSplits:
+// launch_form.h, shared with the host-only weight preparation)
 // MFMA K-slabs per (chunk, tap): two halves of the chunk, or for kF16x3 the three
 // products (w_hi,x_hi) (w_lo,x_hi) (w_hi,x_lo) over the chunk's 32 channels.
 inline int slabsPerTap(int prec) { return prec == kF16x3 ? 3 : 2; }
-// Packed weight records per (chunk, tap): the two K halves, or for kF16x3 (w_hi, w_lo)
-// -- w_hi serves both of its products from registers.
-inline int recordsPerTap(int) { return 2; }
-// 1-KiB-per-fragment weight records per channel chunk.  kF16m8 (chunks go in pairs A, B): per
-// tap one f16 record for each chunk (w_hi) plus two records holding the 32 fp8 bytes per lane of
-// the MX operand (k-group g: chunk g>>1, g&1 ? e4m3(w_hi) : e4m3(w_lo)) -- 4 per tap and pair.
-inline int recordsPerChunk(int taps, int prec) {
-    return isMx(prec) ? 2 * taps : taps * recordsPerTap(prec);
-}
-// Input channels are padded to whole chunks; kF16m8 to whole chunk pairs.
-inline int inputChannelGranule(int prec) { return isMx(prec) ? 2 * chunkChannels(prec) : chunkChannels(prec); }
 
 // ---- feature-plane expansion (reference K1/K2, src/cuda/extractbit.cu) ----
 hipError_t launchExtractBitsNCHW(float* dst, const uint64_t* src, int batch,
@@ -120,7 +106,7 @@ hipError_t launchCoopTrunk(const void* devLayers, int nLayers, int batch, int co
 typedef unsigned int team_u32x4 __attribute__((ext_vector_type(4)));
 struct TeamLayer {
     const unsigned char* x;   // [boards][81][kdim] kF16x3
-    const team_u32x4* w;      // kF16x3 records of the layer (packTileWeights)
+    const team_u32x4* w;      // kF16x3 records of the layer (net_prepare.h)
     const float* bias;        // [cout]
     const unsigned char* res; // residual, layout of y, or null
     unsigned char* y;         // [boards][81][cout] kF16x3
@@ -164,7 +150,6 @@ hipError_t launchHeads(const void* x, const void* wfrag, const float* bias,
 // denseSplits(kdim, prec) slices K_z of the input channels (a one-wave workgroup walks its
 // chunks serially, one global-load latency each; 9 slices cut that chain 9x: 56 -> 9 us).
 // The partial sums are added in a fixed order, with the bias and the ReLU, by launchValueOut.
-int denseSplits(int kdim, int prec);
 hipError_t launchDense(const void* x, const void* wfrag, const float* bias,
                        float* y, int rows, int kdim, int cout, size_t partStride,
                        float accScale, int prec, hipStream_t stream);
@@ -182,19 +167,7 @@ hipError_t launchValueOut(const float* h, const float* b1, int nsplit, size_t pa
 hipError_t launchGatherLogits(const float* policy, const uint16_t* idx, const uint32_t* offsets,
                               float* out, int batch, int softmax, hipStream_t stream);
 
-// Fragment-ordered weights: number of 16-byte lane records INCLUDING the eight
-// trailing zero slabs the kernel's prefetch may touch.
-size_t tileWeightRecords(int taps, int kdim, int cout, int prec);
-// Host-side re-layout.  get(n, k, tap) returns the (already BN-folded) weight
-// of output channel n, input channel k (< kReal), tap (< taps); input
-// channels [kReal, kdim) are zero padding, as are output channels for which
-// get() returns 0.
-typedef float (*WeightGetter)(const void* ctx, int n, int k, int tap);
-// `scale` multiplies every weight before conversion (a power of two chosen per
-// tensor for kF16x3 so hi and lo stay in f16's normal range; the kernel undoes it
-// exactly through accScale = 1/scale).
-void packTileWeights(WeightGetter get, const void* ctx, int taps, int kReal,
-                     int kdim, int cout, int prec, float scale, void* dst);
+// (the host-side re-layout into fragment order, packTileWeights: net_prepare.h)
 
 // Debug: activations [batch][81][c] T -> f32 [batch][c][81].
 hipError_t launchActToNCHW(const void* x, float* dst, int batch, int c,

@@ -5,6 +5,8 @@
 #ifndef NSG_LAUNCH_FORM_H
 #define NSG_LAUNCH_FORM_H
 
+#include <stddef.h>
+
 namespace nsg {
 
 // (the arithmetic of each precision: kernels/kernels.h)
@@ -13,6 +15,41 @@ enum Precision { kFp32 = 0, kFp16 = 1, kBf16 = 2, kF16x3 = 3, kF16m8 = 4, kF16m6
 constexpr bool isMx(int prec) { return prec == kF16m8 || prec == kF16m6; }
 // Precision of the 1x1 heads / value MLP of an evaluator whose trunk runs at `prec`.
 inline int headPrecision(int prec) { return isMx(prec) ? (int)kF16x3 : prec; }
+
+// What the kernels (kernels/kernels.h) and the host-only weight preparation (net_prepare.h) both read of a precision.
+constexpr int kM8WLoShift = 10;  // weight record  = e4m3(w_lo * 2^10)
+constexpr int kM8WHiShift = -2;  // weight record  = e4m3(w_hi * 2^-2); both products carry 2^-10
+// Bytes one activation channel occupies (a kF16x3 pair is 2 + 2 bytes, kF16m8 2 + 1 + 1).
+inline int elemSize(int prec) { return (prec == kFp32 || prec == kF16x3 || isMx(prec)) ? 4 : 2; }
+// Channels per 128-byte K chunk of the trunk convolution.
+inline int chunkChannels(int prec) { return 128 / elemSize(prec); }
+// Packed weight records per (chunk, tap): the two K halves, or for kF16x3 (w_hi, w_lo)
+// -- w_hi serves both of its products from registers.
+inline int recordsPerTap(int) { return 2; }
+// 1-KiB-per-fragment weight records per channel chunk.  kF16m8 (chunks go in pairs A, B): per
+// tap one f16 record for each chunk (w_hi) plus two records holding the 32 fp8 bytes per lane of
+// the MX operand (k-group g: chunk g>>1, g&1 ? e4m3(w_hi) : e4m3(w_lo)) -- 4 per tap and pair.
+inline int recordsPerChunk(int taps, int prec) {
+    return isMx(prec) ? 2 * taps : taps * recordsPerTap(prec);
+}
+// Input channels are padded to whole chunks; kF16m8 to whole chunk pairs.
+inline int inputChannelGranule(int prec) { return isMx(prec) ? 2 * chunkChannels(prec) : chunkChannels(prec); }
+// Fragment-ordered weights: number of 16-byte lane records INCLUDING the
+// trailing zero slabs the kernel's prefetch may touch.
+inline size_t tileWeightRecords(int taps, int kdim, int cout, int prec) {
+    const int nkc = kdim / chunkChannels(prec);
+    const size_t nft = (size_t)(cout / 16);
+    if (prec == kF16m6) // packed MX slabs: per tap and chunk pair nft x (1024 + 1024 + 1600) bytes (mfma_tile.h, kPackX)
+        return (size_t)(nkc / 2) * taps * nft * 3648 / 16 + 16 * nft * 64;
+    return ((size_t)nkc * recordsPerChunk(taps, prec) + 16) * nft * 64; // + 16 zero records: deepest prefetch
+}
+// K slices of the value MLP's first layer (launchDense, kernels/kernels.h).
+inline int denseSplits(int kdim, int prec) {
+    const int nkc = kdim / chunkChannels(prec);
+    for (int s = 9; s > 1; --s)
+        if (nkc % s == 0) return s;
+    return 1;
+}
 
 struct ConvPlan {
     int nb;      // boards per workgroup

@@ -8,6 +8,7 @@
 // every compute entry fails with NSG_E_HIP when no device is usable.
 #include "../../include/nsg.h"
 #include "kernels/kernels.h"
+#include "net_prepare.h"
 #include "onnx_reader.h"
 #include "onnx_graph.h"
 #include "graph_exec.h"
@@ -23,7 +24,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -31,9 +31,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
-#include <random>
 #include <string>
-#include <thread>
 #include <vector>
 
 namespace {
@@ -180,131 +178,6 @@ struct GraphWeights {
     }
 };
 
-// Parsed view of an NSGW v1 blob (DESIGN.md "Weight file").
-struct NetView {
-    int cin, F, blocks, pc, vc, vh;
-    float eps;
-    const float* stemW; const float* stemBn;
-    std::vector<const float*> w1, bn1, w2, bn2;
-    const float* polW; const float* polB;
-    const float* valW; const float* valBn;
-    const float* fc1W; const float* fc1B;
-    const float* fc2W; const float* fc2B;
-    uint64_t params;
-};
-
-int parseBlob(const void* blob, size_t size, NetView* nv) {
-    if (size < 64) return fail(NSG_E_FORMAT, "weight blob too small (%zu bytes)", size);
-    const unsigned char* p = (const unsigned char*)blob;
-    if (memcmp(p, "NSGW", 4) != 0) return fail(NSG_E_FORMAT, "bad magic (not an NSGW file)");
-    uint32_t h[15];
-    memcpy(h, p + 4, sizeof(h));
-    if (h[0] != 1) return fail(NSG_E_FORMAT, "unsupported NSGW version %u", h[0]);
-    nv->cin = (int)h[1]; nv->F = (int)h[2]; nv->blocks = (int)h[3];
-    nv->pc = (int)h[4]; nv->vc = (int)h[5]; nv->vh = (int)h[6];
-    memcpy(&nv->eps, &h[7], 4);
-    const size_t F = nv->F, C = nv->cin, VC = nv->vc, VH = nv->vh, PC = nv->pc;
-    if (F == 0 || C == 0 || VC == 0 || VH == 0 || PC == 0 || nv->blocks < 0)
-        return fail(NSG_E_FORMAT, "zero dimension in NSGW header");
-    const size_t need = F * C * 9 + 4 * F + (size_t)nv->blocks * 2 * (F * F * 9 + 4 * F) +
-                        PC * F + PC + VC * F + 4 * VC + VH * VC * 81 + VH + 2 * VH + 2;
-    if (size != 64 + need * sizeof(float))
-        return fail(NSG_E_FORMAT, "NSGW size mismatch: have %zu, header implies %zu", size,
-                    64 + need * sizeof(float));
-    nv->params = need;
-    const float* f = (const float*)(p + 64);
-    nv->stemW = f; f += F * C * 9;
-    nv->stemBn = f; f += 4 * F;
-    nv->w1.resize(nv->blocks); nv->bn1.resize(nv->blocks);
-    nv->w2.resize(nv->blocks); nv->bn2.resize(nv->blocks);
-    for (int k = 0; k < nv->blocks; ++k) {
-        nv->w1[k] = f; f += F * F * 9;
-        nv->bn1[k] = f; f += 4 * F;
-        nv->w2[k] = f; f += F * F * 9;
-        nv->bn2[k] = f; f += 4 * F;
-    }
-    nv->polW = f; f += PC * F;
-    nv->polB = f; f += PC;
-    nv->valW = f; f += VC * F;
-    nv->valBn = f; f += 4 * VC;
-    nv->fc1W = f; f += VH * VC * 81;
-    nv->fc1B = f; f += VH;
-    nv->fc2W = f; f += 2 * VH;
-    nv->fc2B = f; f += 2;
-    return NSG_OK;
-}
-
-// What the specialised loader refuses in a parsed blob (NSG_E_FORMAT): an ONNX model it refuses goes to the general
-// graph path instead.
-int checkSpecialised(const NetView& nv, int numChannels) {
-    if (nv.cin != numChannels)
-        return fail(NSG_E_FORMAT, "weight file expects %d input planes, evaluator has %d", nv.cin, numChannels);
-    // trt.cc:193-210: the policy output must have ml::MoveIndexMax elements
-    if (nv.pc * NSG_NUM_SQUARES != NSG_MOVE_INDEX_MAX)
-        return fail(NSG_E_FORMAT, "Unexpected PolicySize: %d (expected: %d).",
-                    nv.pc * NSG_NUM_SQUARES, NSG_MOVE_INDEX_MAX);
-    if (nv.F % 64 != 0) return fail(NSG_E_FORMAT, "trunk width %d is not a multiple of 64", nv.F);
-    if (nv.vh % 64 != 0) return fail(NSG_E_FORMAT, "value hidden width %d is not a multiple of 64", nv.vh);
-    return NSG_OK;
-}
-
-// BN folding in double: w' = w * g/sqrt(v+eps), b' = beta - mean * g/sqrt(v+eps)
-void foldBn(const float* bn, int n, float eps, std::vector<double>* scale, std::vector<float>* bias) {
-    scale->resize(n);
-    bias->resize(n);
-    for (int i = 0; i < n; ++i) {
-        const double g = bn[0 * n + i], b = bn[1 * n + i], m = bn[2 * n + i], v = bn[3 * n + i];
-        const double s = g / std::sqrt(v + (double)eps);
-        (*scale)[i] = s;
-        (*bias)[i] = (float)(b - m * s);
-    }
-}
-
-// kF16m8's correction operands are e4m3 copies under FIXED scales (kernels.h): x_hi as it is and
-// x_lo * 2^12 must stay below 448, i.e. activations below ~224 (an f16 residual is at most 2^-11 of its
-// value); beyond that the copies clamp and the error drifts from 1e-4 towards plain f16's 1e-2
-// (profiles/r02/c_envelope_sweep.txt).  The bound is estimated from the WEIGHTS at load time by pushing
-// a second moment through the folded layers -- uncorrelated inputs: E[y_c^2] = |w'_c|^2 E[x^2] + b'_c^2,
-// a ReLU keeps half of it, a residual add sums the branches -- and taking six standard deviations of the
-// widest channel.  Crude (it ignores correlations) but monotone in what matters: BN gains, weight norms.
-struct MomentNet {
-    double x2 = 1.0; // second moment per input value entering the next layer
-    double peak = 0.0;
-};
-void pushConvMoment(const float* w, const double* scale, const float* bias, int cout, int cin, int taps,
-                    double in2, double* out2Max, double* out2Mean) {
-    double worst = 0.0, mean = 0.0;
-    for (int n = 0; n < cout; ++n) {
-        double ss = 0.0;
-        const float* wn = w + (size_t)n * cin * taps;
-        for (int k = 0; k < cin * taps; ++k) ss += (double)wn[k] * wn[k];
-        const double y2 = ss * scale[n] * scale[n] * in2 + (double)bias[n] * bias[n];
-        worst = std::max(worst, y2);
-        mean += y2;
-    }
-    *out2Max = worst;
-    *out2Mean = mean / cout;
-}
-
-struct Conv3Ctx { const float* w; const double* scale; int cin; };
-float conv3Get(const void* c, int n, int k, int tap) {
-    const Conv3Ctx* x = (const Conv3Ctx*)c;
-    return (float)((double)x->w[((size_t)n * x->cin + k) * 9 + tap] * x->scale[n]);
-}
-struct HeadsCtx { const float* valW; const double* valScale; const float* polW; int F, vc, pc; };
-float headsGet(const void* c, int n, int k, int) {
-    const HeadsCtx* x = (const HeadsCtx*)c;
-    if (n < x->vc) return (float)((double)x->valW[(size_t)n * x->F + k] * x->valScale[n]);
-    if (n < x->vc + x->pc) return x->polW[(size_t)(n - x->vc) * x->F + k];
-    return 0.f;
-}
-struct Fc1Ctx { const float* w; int vc; };
-float fc1Get(const void* c, int n, int k, int) {
-    const Fc1Ctx* x = (const Fc1Ctx*)c;
-    const int sq = k / x->vc, ch = k - sq * x->vc; // device K index = sq*VC + c
-    return x->w[(size_t)n * x->vc * 81 + (size_t)ch * 81 + sq];
-}
-
 constexpr int kMaxEventPairs = 1024;
 
 } // namespace
@@ -358,6 +231,7 @@ struct nsg_evaluator {
     // weights and tiles through buffer descriptors: +1.6-2.4 % at 512, -3..-7 % at 160-192; r1: +-0 % kF16m8, -6 % kF16x3.)
     int useTrunkKernel = -1;
 
+    nsg::TrunkSequence seq;   // the 3x3 layers' buffers and weights in launch order (net_prepare.h), built by finishLoad
     void* trunkOut = nullptr; // which act[] holds the trunk output of the last forward
 
     // Team trunk (kernels/team_trunk.hip): up to sixteen boards, every 3x3 layer in one persistent launch, kF16x3
@@ -375,8 +249,8 @@ struct nsg_evaluator {
     uint64_t teamFallbacks = 0; // team launches that gave up and were re-run on the per-layer kernels (nsg_get_team_stats)
     int teamLockedOut = 0;      // another PROCESS holds this device's team token (teamDeviceLock): per-layer kernels only
     bool teamLockHeld = false;  // this evaluator holds a reference on the process's lock of the device
-    // Cooperative trunk (mfma_tile.h, coopTrunkKernel): the two-way K split of 65 ... CUs/2 boards as ONE launch whose
-    // two workgroups per board hand their halves to each other.  NSG_COOP_TRUNK=0 switches it off.  Shares the team
+    // Cooperative trunk (mfma_tile.h, coopTrunkKernel): a K-split plan of a kF16m6 net (17 boards upward: launch_form.h,
+    // canRunCoopTrunk) as ONE launch whose workgroups per board hand their output slices to each other.  NSG_COOP_TRUNK=0 switches it off.  Shares the team
     // trunk's device token (both need every workgroup of their grid resident), status word and recovery.
     DevBuf coopFlags;           // [batchMax][members] unsigned; values count on from launch to launch (coopFlagBase)
     unsigned coopFlagBase = 0;  // first flag value of the next cooperative launch
@@ -456,51 +330,18 @@ int drainProfile(nsg_evaluator* ev) {
     return NSG_OK;
 }
 
-// Host half of a layer upload: picks the power-of-two weight scale and packs the fragment
-// records.  Pure function of its arguments (runs on worker threads at load time).
-void packLayer(nsg::WeightGetter get, const void* ctx, int taps, int kReal, int kdim, int cout,
-               int coutReal, int prec, std::vector<unsigned char>* host, float* accScale) {
-    host->assign(nsg::tileWeightRecords(taps, kdim, cout, prec) * 16, 0);
-    float scale = 1.f;
-    if (prec == nsg::kF16x3 || nsg::isMx(prec)) {
-        // power-of-two scale putting the largest |w| in [2^8, 2^9): hi and lo of every
-        // weight that matters stay in f16's normal range; undone exactly by accScale
-        float maxAbs = 0.f;
-        for (int n = 0; n < coutReal; ++n)
-            for (int k = 0; k < kReal; ++k)
-                for (int t = 0; t < taps; ++t) maxAbs = std::fmax(maxAbs, std::fabs(get(ctx, n, k, t)));
-        if (maxAbs > 0.f && std::isfinite(maxAbs)) {
-            int e = 0;
-            std::frexp(maxAbs, &e); // maxAbs = m * 2^e, m in [0.5, 1)
-            scale = std::ldexp(1.0f, 9 - e);
-        }
-    }
-    *accScale = 1.0f / scale;
-    nsg::packTileWeights(get, ctx, taps, kReal, kdim, cout, prec, scale, host->data());
-}
-
-// Device half: allocation and copies (caller's thread, bound to the evaluator's device).
-int commitLayer(const std::vector<unsigned char>& host, float accScale, int kdim, int cout,
-                const std::vector<float>& bias, ConvLayer* L) {
-    L->accScale = accScale;
-    int rc = L->w.alloc(host.size(), false);
+// Uploads one prepared layer (caller's thread, bound to the evaluator's device) and releases its host image.
+int commitLayer(nsg::PreparedLayer& P, ConvLayer* L) {
+    L->accScale = P.accScale;
+    int rc = L->w.alloc(P.image.size(), false);
     if (rc) return rc;
-    NSG_HIP(hipMemcpy(L->w.p, host.data(), host.size(), hipMemcpyHostToDevice));
-    std::vector<float> b(cout, 0.f);
-    for (size_t i = 0; i < bias.size() && i < (size_t)cout; ++i) b[i] = bias[i];
-    rc = L->bias.alloc((size_t)cout * 4, false);
+    NSG_HIP(hipMemcpy(L->w.p, P.image.data(), P.image.size(), hipMemcpyHostToDevice));
+    std::vector<unsigned char>().swap(P.image);
+    rc = L->bias.alloc(P.bias.size() * 4, false);
     if (rc) return rc;
-    NSG_HIP(hipMemcpy(L->bias.p, b.data(), (size_t)cout * 4, hipMemcpyHostToDevice));
-    L->cin = kdim;
+    NSG_HIP(hipMemcpy(L->bias.p, P.bias.data(), P.bias.size() * 4, hipMemcpyHostToDevice));
+    L->cin = P.cin;
     return NSG_OK;
-}
-
-int uploadLayer(nsg::WeightGetter get, const void* ctx, int taps, int kReal, int kdim,
-                int cout, int coutReal, int prec, const std::vector<float>& bias, ConvLayer* L) {
-    std::vector<unsigned char> host;
-    float accScale = 1.f;
-    packLayer(get, ctx, taps, kReal, kdim, cout, coutReal, prec, &host, &accScale);
-    return commitLayer(host, accScale, kdim, cout, bias, L);
 }
 
 int roundUp(int a, int b) { return (a + b - 1) / b * b; }
@@ -638,9 +479,19 @@ int enqueueHeads(nsg_evaluator* ev, void* x, int off, int count, int hprec, hipS
     return NSG_OK;
 }
 
-// The output of the persistent launches' layer list: the buffer its rotation ends in.
+// What a step of ev->seq names: a buffer of the evaluator, the weights of a layer (x3: in the kF16x3 copy of the trunk).
+void* trunkBuffer(const nsg_evaluator* ev, int buf) {
+    return buf == nsg::kBufNone ? nullptr : buf == nsg::kBufPlanes ? ev->planes.p : ev->act[buf - nsg::kBufAct0].p;
+}
+const ConvLayer& trunkWeights(const NetWeights& N, const nsg::TrunkStep& t, bool x3) {
+    if (t.weights == nsg::kStem) return x3 ? N.stemX3 : N.stem;
+    if (t.weights == nsg::kConv1) return (x3 ? N.conv1X3 : N.conv1)[(size_t)t.block];
+    return (x3 ? N.conv2X3 : N.conv2)[(size_t)t.block];
+}
+
+// The output of the persistent launches' layer list: the buffer the sequence ends in.
 void* trunkListOutput(nsg_evaluator* ev) {
-    return ev->trunkOut = (ev->blocks % 2 == 1) ? ev->act[2].p : ev->act[0].p;
+    return ev->trunkOut = trunkBuffer(ev, ev->seq.outBuf);
 }
 
 // The whole forward of a batch of at most kTeamMaxBoards boards with the team trunk (under the device's token).
@@ -733,46 +584,36 @@ int enqueueWholeTrunk(nsg_evaluator* ev, int B, const nsg::ConvPlan& plan, hipSt
 int enqueueChain(nsg_evaluator* ev, int off, int count, const nsg::ConvPlan& plan, int prec, hipStream_t s,
                  bool stampsOk, hipEvent_t trunkBegin = nullptr, hipEvent_t trunkEnd = nullptr) {
     const bool x3Fallback = prec != ev->prec;
-    const ConvLayer& stem = x3Fallback ? ev->W->stemX3 : ev->W->stem;
-    const std::vector<ConvLayer>& conv1 = x3Fallback ? ev->W->conv1X3 : ev->W->conv1;
-    const std::vector<ConvLayer>& conv2 = x3Fallback ? ev->W->conv2X3 : ev->W->conv2;
     const size_t es = (size_t)nsg::elemSize(prec);
-    auto act = [&](void* base, size_t rowElems) { return (void*)((unsigned char*)base + (size_t)off * rowElems * es); };
+    // this chain's boards of the sequence's four buffers
+    void* buf[4];
+    for (int b = nsg::kBufPlanes; b <= nsg::kBufAct2; ++b)
+        buf[b] = (unsigned char*)trunkBuffer(ev, b) + (size_t)off * 81 * (b == nsg::kBufPlanes ? ev->cpad : ev->F) * es;
     const uint64_t* input = (const uint64_t*)ev->input.p + (size_t)off * ev->numChannels * 2;
-    void* planes = act(ev->planes.p, (size_t)81 * ev->cpad);
     // feature planes (replaces cuda::extractBits, trt.cc:255-258)
     {
         Range r("nsg.planes");
-        NSG_HIP(nsg::launchExtractBitsAct(planes, input, count, ev->numChannels, ev->cpad, prec, s));
+        NSG_HIP(nsg::launchExtractBitsAct(buf[nsg::kBufPlanes], input, count, ev->numChannels, ev->cpad, prec, s));
     }
     const int hprec = nsg::headPrecision(prec); // kF16m8: the last trunk layer writes the kF16x3 layout
-    void* x = act(ev->act[0].p, (size_t)81 * ev->F);
+    void* x = buf[ev->seq.outBuf];
     {
         Range trunkRange("nsg.trunk");
         // stem + residual trunk
-        void* y = act(ev->act[1].p, (size_t)81 * ev->F);
-        void* z = act(ev->act[2].p, (size_t)81 * ev->F);
-        NSG_HIP(nsg::launchConv3x3(planes, stem.w.p, (const float*)stem.bias.p, nullptr, x, count,
-                                   ev->cpad, ev->F, 1, stem.accScale, prec, plan, s, nullptr,
-                                   hprec != prec && ev->blocks == 0));
-        if (trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
-        for (int k = 0; k < ev->blocks; ++k) {
-            unsigned long long* st1 = nullptr;
-            unsigned long long* st2 = nullptr;
+        const int nl = (int)ev->seq.steps.size();
+        for (int i = 0; i < nl; ++i) {
+            const nsg::TrunkStep& t = ev->seq.steps[(size_t)i];
+            const ConvLayer& L = trunkWeights(*ev->W, t, x3Fallback);
+            unsigned long long* st = nullptr;
 #ifdef NSG_DIAG_STAMPS
-            if (ev->stamps.p && stampsOk) {
-                st1 = (unsigned long long*)ev->stamps.p + (size_t)(2 * k) * 4096 * 8;
-                st2 = (unsigned long long*)ev->stamps.p + (size_t)(2 * k + 1) * 4096 * 8;
-            }
+            if (ev->stamps.p && stampsOk && i > 0) st = (unsigned long long*)ev->stamps.p + (size_t)(i - 1) * 4096 * 8;
 #else
             (void)stampsOk;
 #endif
-            NSG_HIP(nsg::launchConv3x3(x, conv1[k].w.p, (const float*)conv1[k].bias.p, nullptr, y, count,
-                                       ev->F, ev->F, 1, conv1[k].accScale, prec, plan, s, st1));
-            NSG_HIP(nsg::launchConv3x3(y, conv2[k].w.p, (const float*)conv2[k].bias.p, x, z, count,
-                                       ev->F, ev->F, 1, conv2[k].accScale, prec, plan, s, st2,
-                                       hprec != prec && k == ev->blocks - 1));
-            void* t = x; x = z; z = t;
+            NSG_HIP(nsg::launchConv3x3(buf[t.in], L.w.p, (const float*)L.bias.p, t.residual == nsg::kBufNone ? nullptr : buf[t.residual],
+                                       buf[t.out], count, L.cin, ev->F, 1, L.accScale, prec, plan, s, st,
+                                       hprec != prec && i == nl - 1));
+            if (i == 0 && trunkBegin) NSG_HIP(hipEventRecord(trunkBegin, s));
         }
         if (trunkEnd) NSG_HIP(hipEventRecord(trunkEnd, s));
         if (off == 0) ev->trunkOut = x;
@@ -961,19 +802,16 @@ int finishLoad(nsg_evaluator* ev, std::shared_ptr<NetWeights> W) {
         if ((rc = ev->act[i].alloc(bpad * 81 * N.F * es, true))) return rc;
     if ((rc = ev->vfeat.alloc((size_t)ev->batchMax * ev->fc1K * es, true))) return rc;
     if ((rc = ev->hidden.alloc((size_t)ev->batchMax * N.vh * 4 * nsg::denseSplits(ev->fc1K, nsg::headPrecision(prec)), true))) return rc;
-    {   // persistent-trunk layer list, same buffer rotation as the per-layer path
-        const int nl = 1 + 2 * N.blocks;
+    ev->seq = nsg::trunkSequence(N.blocks);
+    const int nl = (int)ev->seq.steps.size();
+    {   // persistent-trunk layer list
         std::vector<unsigned char> host((size_t)nl * nsg::trunkLayerBytes());
-        void* x = ev->act[0].p; void* y = ev->act[1].p; void* z = ev->act[2].p;
-        nsg::fillTrunkLayer(host.data(), 0, ev->planes.p, N.stem.w.p, (const float*)N.stem.bias.p,
-                            nullptr, x, ev->cpad, N.F, 1, N.stem.accScale);
-        for (int k = 0; k < N.blocks; ++k) {
-            nsg::fillTrunkLayer(host.data(), 1 + 2 * k, x, N.conv1[k].w.p, (const float*)N.conv1[k].bias.p,
-                                nullptr, y, N.F, N.F, 1, N.conv1[k].accScale);
-            nsg::fillTrunkLayer(host.data(), 2 + 2 * k, y, N.conv2[k].w.p, (const float*)N.conv2[k].bias.p,
-                                x, z, N.F, N.F, 1, N.conv2[k].accScale,
-                                nsg::isMx(prec) && k == N.blocks - 1);
-            void* t = x; x = z; z = t;
+        for (int i = 0; i < nl; ++i) {
+            const nsg::TrunkStep& t = ev->seq.steps[(size_t)i];
+            const ConvLayer& L = trunkWeights(N, t, false);
+            nsg::fillTrunkLayer(host.data(), i, trunkBuffer(ev, t.in), L.w.p, (const float*)L.bias.p, trunkBuffer(ev, t.residual),
+                                trunkBuffer(ev, t.out), L.cin, N.F, 1, L.accScale,
+                                nsg::isMx(prec) && N.blocks > 0 && i == nl - 1);
         }
         if ((rc = ev->trunkLayers.alloc(host.size(), false))) return rc;
         NSG_HIP(hipMemcpy(ev->trunkLayers.p, host.data(), host.size(), hipMemcpyHostToDevice));
@@ -999,26 +837,18 @@ int finishLoad(nsg_evaluator* ev, std::shared_ptr<NetWeights> W) {
         }
     }
     // team trunk layer list: the kF16x3 copy of the trunk (an MX evaluator keeps one for batches without an MX plan;
-    // a kF16x3 evaluator's own records), same buffer rotation
+    // a kF16x3 evaluator's own records), the same sequence
     ev->teamLayerCount = 0;
     const bool mxHere = nsg::isMx(prec);
     if ((mxHere || prec == nsg::kF16x3) && N.blocks >= 1 && nsg::teamTrunkSupports(N.F, ev->cpad, 1) &&
         (!mxHere || (N.stemX3.w.p && N.conv1X3.size() == (size_t)N.blocks))) {
-        const ConvLayer& stem = mxHere ? N.stemX3 : N.stem;
-        const std::vector<ConvLayer>& c1 = mxHere ? N.conv1X3 : N.conv1;
-        const std::vector<ConvLayer>& c2 = mxHere ? N.conv2X3 : N.conv2;
-        const int nl = 1 + 2 * N.blocks;
         std::vector<nsg::TeamLayer> host((size_t)nl);
-        unsigned char* x = (unsigned char*)ev->act[0].p; unsigned char* y = (unsigned char*)ev->act[1].p;
-        unsigned char* z = (unsigned char*)ev->act[2].p;
-        host[0] = nsg::TeamLayer{(const unsigned char*)ev->planes.p, (const nsg::team_u32x4*)stem.w.p, (const float*)stem.bias.p,
-                                 nullptr, x, ev->cpad, N.F, 1, stem.accScale};
-        for (int k = 0; k < N.blocks; ++k) {
-            host[1 + 2 * k] = nsg::TeamLayer{x, (const nsg::team_u32x4*)c1[k].w.p, (const float*)c1[k].bias.p, nullptr, y,
-                                             N.F, N.F, 1, c1[k].accScale};
-            host[2 + 2 * k] = nsg::TeamLayer{y, (const nsg::team_u32x4*)c2[k].w.p, (const float*)c2[k].bias.p, x, z,
-                                             N.F, N.F, 1, c2[k].accScale};
-            unsigned char* t = x; x = z; z = t;
+        for (int i = 0; i < nl; ++i) {
+            const nsg::TrunkStep& t = ev->seq.steps[(size_t)i];
+            const ConvLayer& L = trunkWeights(N, t, mxHere);
+            host[(size_t)i] = nsg::TeamLayer{(const unsigned char*)trunkBuffer(ev, t.in), (const nsg::team_u32x4*)L.w.p,
+                                             (const float*)L.bias.p, (const unsigned char*)trunkBuffer(ev, t.residual),
+                                             (unsigned char*)trunkBuffer(ev, t.out), L.cin, N.F, 1, L.accScale};
         }
         if ((rc = ev->teamLayers.alloc(host.size() * sizeof(nsg::TeamLayer), false))) return rc;
         NSG_HIP(hipMemcpy(ev->teamLayers.p, host.data(), host.size() * sizeof(nsg::TeamLayer), hipMemcpyHostToDevice));
@@ -1329,111 +1159,33 @@ int nsg_load_memory(nsg_evaluator* ev, const void* blob, size_t size) {
     }
     int rc = bind(ev);
     if (rc) return rc;
-    NetView nv;
-    if ((rc = parseBlob(blob, size, &nv))) return rc;
-    if ((rc = checkSpecialised(nv, ev->numChannels))) return rc;
-
     const int prec = ev->prec;
-    const int kc = nsg::inputChannelGranule(prec); // input channels are padded to whole chunks (kF16m8: chunk pairs)
+    const char* guard = getenv("NSG_M8_GUARD");
+    nsg::PreparedNet P;
+    std::string err;
+    if ((rc = nsg::prepareNet(blob, size, prec, ev->numChannels, !(guard && guard[0] == '0'), &P, &err)))
+        return fail(rc, "%s", err.c_str());
+
     ev->loaded = false;
     auto W = std::make_shared<NetWeights>();
     W->gpu = ev->gpu; W->prec = prec;
-    W->F = nv.F; W->blocks = nv.blocks; W->vc = nv.vc; W->vh = nv.vh; W->cin = nv.cin;
-    W->cpad = roundUp(nv.cin, kc);
-    W->headsCout = roundUp(nv.vc + nv.pc, 64);
-    W->fc1K = roundUp(81 * nv.vc, nsg::chunkChannels(nsg::headPrecision(prec)));
-    W->params = nv.params;
-
-    std::vector<double> scale;
-    std::vector<float> bias;
-    {   // 3x3 layers: BN folding and fragment packing on worker threads, uploads on this one
-        struct Job {
-            std::vector<double> scale;
-            std::vector<float> bias;
-            const float* w;
-            int cinReal, kdim, prec;
-            ConvLayer* L;
-            std::vector<unsigned char> host;
-            float accScale = 1.f;
-        };
-        W->conv1.resize(nv.blocks); W->conv2.resize(nv.blocks);
-        if (nsg::isMx(prec)) { W->conv1X3.resize(nv.blocks); W->conv2X3.resize(nv.blocks); }
-        std::vector<Job> jobs;
-        auto add = [&](const float* w, const float* bn, int cinReal, int kdim, ConvLayer* L, ConvLayer* Lx3) {
-            Job j;
-            foldBn(bn, nv.F, nv.eps, &j.scale, &j.bias);
-            j.w = w; j.cinReal = cinReal; j.kdim = kdim; j.prec = prec; j.L = L;
-            jobs.push_back(j);
-            if (nsg::isMx(prec)) { // the f16x3 copy of the trunk (small batches)
-                j.prec = nsg::kF16x3; j.L = Lx3;
-                jobs.push_back(std::move(j));
-            }
-        };
-        add(nv.stemW, nv.stemBn, nv.cin, W->cpad, &W->stem, &W->stemX3);
-        for (int k = 0; k < nv.blocks; ++k) {
-            add(nv.w1[k], nv.bn1[k], nv.F, nv.F, &W->conv1[k], nsg::isMx(prec) ? &W->conv1X3[k] : nullptr);
-            add(nv.w2[k], nv.bn2[k], nv.F, nv.F, &W->conv2[k], nsg::isMx(prec) ? &W->conv2X3[k] : nullptr);
-        }
-        std::atomic<size_t> next{0};
-        auto work = [&]() {
-            for (size_t i; (i = next.fetch_add(1)) < jobs.size();) {
-                Job& j = jobs[i];
-                Conv3Ctx c{j.w, j.scale.data(), j.cinReal};
-                packLayer(conv3Get, &c, 9, j.cinReal, j.kdim, nv.F, nv.F, j.prec, &j.host, &j.accScale);
-            }
-        };
-        const unsigned hw = std::thread::hardware_concurrency();
-        const size_t nthreads = std::min<size_t>(jobs.size(), std::max(1u, std::min(hw ? hw : 1u, 8u)));
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < nthreads; ++t) pool.emplace_back(work);
-        work();
-        for (auto& t : pool) t.join();
-        for (Job& j : jobs) {
-            if ((rc = commitLayer(j.host, j.accScale, j.kdim, nv.F, j.bias, j.L))) return rc;
-            std::vector<unsigned char>().swap(j.host);
-        }
-    }
-    // heads: [value conv (BN folded) | policy conv | zero pad]
-    {
-        foldBn(nv.valBn, nv.vc, nv.eps, &scale, &bias);
-        std::vector<float> hb(W->headsCout, 0.f);
-        for (int i = 0; i < nv.vc; ++i) hb[i] = bias[i];
-        for (int i = 0; i < nv.pc; ++i) hb[nv.vc + i] = nv.polB[i];
-        HeadsCtx c{nv.valW, scale.data(), nv.polW, nv.F, nv.vc, nv.pc};
-        if ((rc = uploadLayer(headsGet, &c, 1, nv.F, nv.F, W->headsCout, nv.vc + nv.pc, nsg::headPrecision(prec), hb, &W->heads))) return rc;
-    }
-    {
-        std::vector<float> b1(nv.fc1B, nv.fc1B + nv.vh);
-        Fc1Ctx c{nv.fc1W, nv.vc};
-        if ((rc = uploadLayer(fc1Get, &c, 1, 81 * nv.vc, W->fc1K, nv.vh, nv.vh, nsg::headPrecision(prec), b1, &W->fc1))) return rc;
-    }
-    {   // activation bound estimate (see pushConvMoment)
-        std::vector<double> sc;
-        std::vector<float> bi;
-        double worst = 0.0, mean = 0.0, peak2 = 0.0;
-        // feature planes are 0/1 (a handful of scalar planes in [0,1]): second moment <= the plane density, ~0.2
-        foldBn(nv.stemBn, nv.F, nv.eps, &sc, &bi);
-        pushConvMoment(nv.stemW, sc.data(), bi.data(), nv.F, nv.cin, 9, 0.2, &worst, &mean);
-        peak2 = worst;
-        double x2 = 0.5 * mean; // after the ReLU
-        for (int k = 0; k < nv.blocks; ++k) {
-            foldBn(nv.bn1[k], nv.F, nv.eps, &sc, &bi);
-            pushConvMoment(nv.w1[k], sc.data(), bi.data(), nv.F, nv.F, 9, x2, &worst, &mean);
-            peak2 = std::max(peak2, worst);
-            const double y2 = 0.5 * mean;
-            foldBn(nv.bn2[k], nv.F, nv.eps, &sc, &bi);
-            pushConvMoment(nv.w2[k], sc.data(), bi.data(), nv.F, nv.F, 9, y2, &worst, &mean);
-            peak2 = std::max(peak2, worst + x2); // the residual add
-            x2 = 0.5 * (mean + x2);
-        }
-        W->actBound = 6.0 * std::sqrt(peak2);
-        const char* off = getenv("NSG_M8_GUARD");
-        W->outsideM8Window = prec == nsg::kF16m8 && W->actBound > 224.0 && !(off && off[0] == '0');
-    }
-    if ((rc = W->fc2W.alloc((size_t)2 * nv.vh * 4, false))) return rc;
-    if ((rc = W->fc2B.alloc(8, false))) return rc;
-    NSG_HIP(hipMemcpy(W->fc2W.p, nv.fc2W, (size_t)2 * nv.vh * 4, hipMemcpyHostToDevice));
-    NSG_HIP(hipMemcpy(W->fc2B.p, nv.fc2B, 8, hipMemcpyHostToDevice));
+    W->F = P.F; W->blocks = P.blocks; W->vc = P.vc; W->vh = P.vh; W->cin = P.cin;
+    W->cpad = P.cpad; W->headsCout = P.headsCout; W->fc1K = P.fc1K; W->params = P.params;
+    W->actBound = P.actBound; W->outsideM8Window = P.outsideM8Window;
+    // every layer in turn: its host image is released as soon as it is on the device
+    const bool mx = nsg::isMx(prec); // ... holds the trunk in kF16x3 form too
+    W->conv1.resize(P.blocks); W->conv2.resize(P.blocks);
+    if (mx) { W->conv1X3.resize(P.blocks); W->conv2X3.resize(P.blocks); }
+    if ((rc = commitLayer(P.stem, &W->stem)) || (mx && (rc = commitLayer(P.stemX3, &W->stemX3)))) return rc;
+    for (int k = 0; k < P.blocks; ++k)
+        if ((rc = commitLayer(P.conv1[k], &W->conv1[k])) || (mx && (rc = commitLayer(P.conv1X3[k], &W->conv1X3[k]))) ||
+            (rc = commitLayer(P.conv2[k], &W->conv2[k])) || (mx && (rc = commitLayer(P.conv2X3[k], &W->conv2X3[k]))))
+            return rc;
+    if ((rc = commitLayer(P.heads, &W->heads)) || (rc = commitLayer(P.fc1, &W->fc1))) return rc;
+    if ((rc = W->fc2W.alloc(P.fc2W.size() * 4, false))) return rc;
+    if ((rc = W->fc2B.alloc(P.fc2B.size() * 4, false))) return rc;
+    NSG_HIP(hipMemcpy(W->fc2W.p, P.fc2W.data(), P.fc2W.size() * 4, hipMemcpyHostToDevice));
+    NSG_HIP(hipMemcpy(W->fc2B.p, P.fc2B.data(), P.fc2B.size() * 4, hipMemcpyHostToDevice));
     return finishLoad(ev, std::move(W));
 }
 
@@ -1898,7 +1650,7 @@ static void graphInfoFromPlan(const nsg::graph::GraphPlan& P, nsg_graph_info* in
     info->activation_bytes_per_position = P.activationBytesPerPosition;
 }
 
-static void graphInfoFamily(const NetView& nv, int nodes, int prec, nsg_graph_info* info) {
+static void graphInfoFamily(const nsg::NetView& nv, int nodes, int prec, nsg_graph_info* info) {
     info->path = NSG_PATH_SPECIALISED;
     info->precision = prec;
     info->nodes = nodes;
@@ -1932,13 +1684,12 @@ int nsg_inspect_onnx(const void* onnx, size_t size, int num_channels, nsg_graph_
     std::string famErr;
     std::vector<unsigned char> converted;
     if (nsg::onnx::convertToNsgw(onnx, size, &converted, &famErr)) {
-        NetView nv;
-        int rc = parseBlob(converted.data(), converted.size(), &nv);
-        if (rc == NSG_OK && (rc = checkSpecialised(nv, num_channels)) == NSG_OK) {
+        nsg::NetView nv;
+        int rc = nsg::parseBlob(converted.data(), converted.size(), &nv, &famErr);
+        if (rc == NSG_OK && (rc = nsg::checkSpecialised(nv, num_channels, &famErr)) == NSG_OK) {
             graphInfoFamily(nv, nsg::graph::countNodes(onnx, size), NSG_PRECISION_FP32, info);
             return NSG_OK;
         }
-        famErr = gLastError;
     }
     nsg::graph::GraphPlan plan;
     std::string graphErr;
